@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on MI355X: pattern-chars/s of batched backward search
 (count) on a 1 GB sigma=4 DNA text (config 2: FMIndex, 2^20 length-32 patterns that are
-substrings of the text, so all 32 steps execute) as `value`, with every other BASELINE config in
-the same line: `locate` (config 3), `locate_3b` (64 K short patterns, wide intervals), `rlfm`
-(config 4: RLFMIndex over a 1 GB sigma=255 byte text, 2^20 length-16 patterns, with its own
+substrings of the text, so all 32 steps execute) as `value`.  A plain run does that and nothing else:
+it sets up, warms up, times --steps steps (`ms_per_step` = one of them), writes the last step's
+results with --dump-outputs, and prints the line.  With --full every other BASELINE config is
+measured too and lands in the same line: `locate` (config 3), `locate_3b` (64 K short patterns,
+wide intervals), `rlfm` (config 4: RLFMIndex over a 1 GB sigma=255 byte text, 2^20 length-16 patterns, with its own
 roofline and CPU baseline), `value_incl_d2h` (the same batch through the host-pointer entry point)
 and, with --gpus N, config 5: N x 2^20 patterns sharded over N ranks, index replicated, counts and
 positions gathered over RCCL inside the timed region.
@@ -116,7 +118,41 @@ def parse_args(argv=None):
                          "when it holds several) exactly as a run would, and exit -- the print path without a GPU")
     ap.add_argument("--dump-counts", default=None, help=argparse.SUPPRESS)   # tests: gathered counts -> .npy
     ap.add_argument("--pattern-seed", type=int, default=None, help=argparse.SUPPRESS)   # tests: same global set at any N
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, run every other leg as well: counter passes and line census "
+                         "(roofline.traffic), configs 2b, 3, 3b, 4, the accelerators alone, the 64-bit engine, the RCCL "
+                         "checks, the host-pointer entry points, the CPU baseline, the golden hashes, the per-rank report "
+                         "of an N > 1 run (each still has its --no-* switch).  Without it the run sets up, warms up, times "
+                         "--steps steps and prints the line: none of those legs, whatever --no-* says")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the LAST timed step computed -- the arrays a caller of "
+                         "fmx_count_batch_dev receives: s.npy, e.npy, count.npy (float64, exact below 2^53; this rank's "
+                         "patterns in input order, a fixed seeded sample of them beyond DUMP_LIMIT_BYTES) -- into DIR.  "
+                         "Text and patterns are functions of the arguments alone, so two builds can be compared file by file")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+# what a run without --full leaves out (the child modes get their switches from the parent that started them)
+FULL_ONLY = ("no_pmc", "no_census", "no_cpu_baseline", "no_accel", "no_early_exit", "no_rlfm", "no_3b", "no_wide",
+             "no_ic_ab", "no_d2h", "no_config5", "no_rccl_check")
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: 1-D integer array, all of one length} -> path/<name>.npy as float64.  Beyond
+    DUMP_LIMIT_BYTES in all, the same seeded sample of positions (ascending) of every array."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    keep = DUMP_LIMIT_BYTES // (8 * len(arrays))
+    sel = np.sort(np.random.default_rng(20).choice(n, size=keep, replace=False)) if n > keep else None
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        assert a.shape == (n,) and int(a.max(initial=0)) < (1 << 53), name
+        np.save(os.path.join(path, name + ".npy"), (a if sel is None else a[sel]).astype(np.float64))
 
 
 
@@ -132,6 +168,9 @@ def main():
             full = json.loads([ln for ln in txt.splitlines() if ln.startswith("{")][-1])
         print(json.dumps(headline(full, args.headline_of), separators=(",", ":")))
         return
+    if not (args.full or args.pmc_child or args.cabi_child):
+        for k in FULL_ONLY:
+            setattr(args, k, True)
     if args.gpus > 1 and "RANK" not in os.environ:
         # one process per GPU, started before anything in THIS process touches the GPU
         from fm_index_amd import launcher
@@ -248,12 +287,20 @@ def run(args, world, pmc=None, pmc_seconds=0.0, pmc31=None):
     t0 = time.perf_counter()
     ev0.record(stream)
     for _ in range(args.steps):
-        step()
+        last_timed = step()
     pipe.drain()                 # every gather of the timed steps has completed
     ev1.record(stream)
     barrier()
     dt = time.perf_counter() - t0
     dt_rank = dt
+    if args.dump_outputs:
+        # before anything else is launched: (s, e) and the counts as the last timed step left them -- this rank's (at
+        # N > 1: rank 0's slot of the gathered counts; the whole set is what --full hashes)
+        cnt_last = last_timed[rank * wl.npat_pad:rank * wl.npat_pad + npat]
+        dumped = {"s": wl.d_s.cpu().numpy(), "e": wl.d_e.cpu().numpy(), "count": cnt_last.cpu().numpy()}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, dumped)
+        del dumped, cnt_last
     if use_dist:
         tt = torch.tensor([dt], dtype=torch.float64, device="cpu" if gloo else dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -330,18 +377,19 @@ def run(args, world, pmc=None, pmc_seconds=0.0, pmc31=None):
         # ... and over the (s, e) pairs, gathered once outside the timed region
         "ranges_sha256": ranges_sha,
     }
-    gold = golden_counts_sha(wl, args)
+    gold = golden_counts_sha(wl, args) if args.full else None
     if gold is not None:
         # tests/golden/config5_counts.json: made by the CPU oracle over ALL patterns of this set
         out["matches_golden"] = {"counts_sha256": gold[0] == counts_sha, "ranges_sha256": gold[1] == ranges_sha,
                                  "source": "tests/golden/config5_counts.json (CPU oracle over all patterns)"}
         assert gold[0] == counts_sha and gold[1] in (None, ranges_sha), \
             "results on the config-5 pattern set differ from tests/golden/config5_counts.json"
-    if use_dist:
+    if use_dist and args.full:
         dist_report(out, torch, dist, sharding, pipe, wl, args, world, rank, local, gloo, dt_rank, ev_ms,
                     kernel_ms_single, step)
 
-    single = world == 1 and rank == 0 and not use_dist          # the default line: every BASELINE config
+    # the line of `--full` at N = 1: every BASELINE config
+    single = world == 1 and rank == 0 and not use_dist and args.full
     # ---- config 2b: uniform random patterns -> the early exit of wrapper.rs:111-113 ----
     rflat = None
     if wl.dna and single and not args.no_early_exit:
@@ -368,7 +416,7 @@ def run(args, world, pmc=None, pmc_seconds=0.0, pmc31=None):
     lap("accelerators")
 
     # ---- locate (config 3; gathered over the ranks for N > 1) ----
-    if wl.level is not None:
+    if wl.level is not None and args.full:
         locate_leg(out, wl, args, world, rank, dist, gloo, key)
 
     # ---- the reference's own row-order sampling on the same index (FMX_FLAG_ROW_ORDER): same positions ----

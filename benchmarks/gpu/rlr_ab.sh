@@ -4,7 +4,7 @@ mkdir -p gpurun_out/r06
 M=$PWD/fm_index_amd/libfmx_measure.so
 run() {
   echo "$*"
-  env FMX_LIB=$M "$@" timeout 600 python3 bench.py --workload rep-rlfm --steps 10 --warmup 3 --no-cpu-baseline --no-pmc --no-census --no-d2h --no-accel --no-rccl-check --no-wide --no-ic-ab --no-config5 --no-early-exit --detail-out gpurun_out/r06/rlr_tmp.json 2>/dev/null | python3 -c "
+  env FMX_LIB=$M "$@" timeout 600 python3 bench.py --full --workload rep-rlfm --steps 10 --warmup 3 --no-cpu-baseline --no-pmc --no-census --no-d2h --no-accel --no-rccl-check --no-wide --no-ic-ab --no-config5 --no-early-exit --detail-out "$(mktemp -d)/rlr_tmp.json" 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('   ', {k: d.get(k) for k in ('locate_hits_per_s','locate_ms_per_batch')})"

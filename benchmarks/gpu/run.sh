@@ -54,7 +54,7 @@ variant)
   export FMX_LIB=$PWD/fm_index_amd/libfmx_measure.so
   for v in $LIST; do
     T=$(echo $v | tr -c 'A-Za-z0-9=\n' _)
-    ( [ "$v" != x ] && export $(echo $v | tr , ' '); timeout 900 python3 bench.py --no-pmc --no-census --no-cpu-baseline --no-accel --no-early-exit --no-d2h --no-wide --no-ic-ab --no-config5 --no-rccl-check "$@" --detail-out $O/variant_$T.json > /dev/null 2> $O/variant_$T.err )
+    ( [ "$v" != x ] && export $(echo $v | tr , ' '); timeout 900 python3 bench.py --full --no-pmc --no-census --no-cpu-baseline --no-accel --no-early-exit --no-d2h --no-wide --no-ic-ab --no-config5 --no-rccl-check "$@" --detail-out $O/variant_$T.json > /dev/null 2> $O/variant_$T.err )
     python3 - $O/variant_$T.json "$v" <<'PY'
 import json, sys
 try:
@@ -69,7 +69,7 @@ PY
 ablib)
   LIST=$1; shift
   for v in $LIST; do
-    ( export FMX_LIB=$PWD/fm_index_amd/$v; timeout 900 python3 bench.py --no-pmc --no-census --no-cpu-baseline --no-accel --no-early-exit --no-d2h --no-wide --no-ic-ab --no-config5 --no-rccl-check "$@" --detail-out $O/ablib_$v.json > /dev/null 2> $O/ablib_$v.err )
+    ( export FMX_LIB=$PWD/fm_index_amd/$v; timeout 900 python3 bench.py --full --no-pmc --no-census --no-cpu-baseline --no-accel --no-early-exit --no-d2h --no-wide --no-ic-ab --no-config5 --no-rccl-check "$@" --detail-out $O/ablib_$v.json > /dev/null 2> $O/ablib_$v.err )
     python3 - $O/ablib_$v.json "$v" <<'PY'
 import json, sys
 try:

@@ -17,12 +17,12 @@ cd /tmp && export TMPDIR=/tmp
 # 20 timed steps: the first launches of a kernel in a process run slower (cold TLB / caches: 0.70-0.77 ms against 0.63-0.65
 # for the count kernel) and must not weigh on the per-kernel average the bench line is compared with
 RD="TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum"
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-pmc --no-census --no-early-exit --no-d2h --no-wide --no-config5 --no-rccl-check --no-ic-ab ${2:---no-accel}"
+ARGS="--full --steps 20 --warmup 5 --no-cpu-baseline --no-pmc --no-census --no-early-exit --no-d2h --no-wide --no-config5 --no-rccl-check --no-ic-ab ${2:---no-accel}"
 rocprofv3 --kernel-trace --stats -d $OUT/trace --output-format csv -- python3 $REPO/bench.py $ARGS --detail-out $OUT/bench_trace_detail.json > $OUT/bench_trace.json 2> $OUT/trace.err
 rocprofv3 --pmc $RD --kernel-trace -d $OUT/pmc_fetch --output-format csv -- python3 $REPO/bench.py --pmc-child > $OUT/pmc_fetch.out 2> $OUT/pmc_fetch.err
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc_write --output-format csv -- python3 $REPO/bench.py --pmc-child > $OUT/pmc_write.out 2> $OUT/pmc_write.err
 # config 4b (repetitive text, RLFM): fmx_locate_rl_rounds_kernel (fmx_locate_rl_lane_kernel until round 5) -- its own trace and counter passes
-rocprofv3 --kernel-trace --stats -d $OUT/trace4b --output-format csv -- python3 $REPO/bench.py --workload rep-rlfm --steps 10 --warmup 3 --no-cpu-baseline --no-pmc --no-census --no-d2h --no-accel --no-rccl-check --detail-out $OUT/bench_trace4b_detail.json > $OUT/bench_trace4b.json 2> $OUT/trace4b.err
+rocprofv3 --kernel-trace --stats -d $OUT/trace4b --output-format csv -- python3 $REPO/bench.py --full --workload rep-rlfm --steps 10 --warmup 3 --no-cpu-baseline --no-pmc --no-census --no-d2h --no-accel --no-rccl-check --detail-out $OUT/bench_trace4b_detail.json > $OUT/bench_trace4b.json 2> $OUT/trace4b.err
 rocprofv3 --pmc $RD --kernel-trace -d $OUT/pmc_fetch4b --output-format csv -- python3 $REPO/bench.py --pmc-child --workload rep-rlfm > $OUT/pmc_fetch4b.out 2> $OUT/pmc_fetch4b.err
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc_write4b --output-format csv -- python3 $REPO/bench.py --pmc-child --workload rep-rlfm > $OUT/pmc_write4b.out 2> $OUT/pmc_write4b.err
 # keep only the small summaries (the full traces can be large)

@@ -199,3 +199,20 @@ def test_the_line_survives_oversized_and_failed_legs(tmp_path):
     line = json.loads(last)
     assert line["legs_failed"] == ["wide"] and "rlfm_value" not in line and line["kernel_ms_max"] == 7.6
     assert CONTRACT_KEYS <= set(line)
+
+
+def test_dump_outputs_writes_float64_and_samples_large_outputs_the_same_way_every_time(tmp_path, monkeypatch):
+    """--dump-outputs: <name>.npy in float64; beyond the size limit every array keeps the same seeded positions"""
+    import numpy as np
+    a = {"s": np.arange(1000, dtype=np.int64) * 3, "e": np.arange(1000, dtype=np.int64) * 3 + 1}
+    B.dump_outputs(str(tmp_path / "all"), a)
+    got = {k: np.load(str(tmp_path / "all" / (k + ".npy"))) for k in a}
+    assert all(got[k].dtype == np.float64 and (got[k] == a[k]).all() for k in a)
+    monkeypatch.setattr(B, "DUMP_LIMIT_BYTES", 2 * 8 * 100)
+    for d in ("x", "y"):
+        B.dump_outputs(str(tmp_path / d), a)
+    x = {k: np.load(str(tmp_path / "x" / (k + ".npy"))) for k in a}
+    y = {k: np.load(str(tmp_path / "y" / (k + ".npy"))) for k in a}
+    assert x["s"].shape == (100,) and sum(v.nbytes for v in x.values()) <= 2 * 8 * 100
+    assert (x["s"] == y["s"]).all() and (x["e"] == y["e"]).all()
+    assert (x["e"] == x["s"] + 1).all() and (np.diff(x["s"]) > 0).all() and (x["s"] % 3 == 0).all()

@@ -12,7 +12,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
-COMMON = ["--log2n", "16", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-accel", "--no-rlfm",
+COMMON = ["--full", "--log2n", "16", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-accel", "--no-rlfm",
           "--no-pmc", "--no-3b", "--no-d2h", "--no-early-exit", "--no-wide", "--pattern-seed", "7"]
 
 
@@ -158,3 +158,32 @@ def test_default_line_carries_config5_at_one_gpu(tmp_path):
     strong = _bench(small + ["--gpus", "1", "--total-patterns", "65536", "--no-cpu-baseline", "--no-locate"],
                     tmp_path, "strong")
     assert strong["counts_sha256"] == c5["counts_sha256"] and strong["ranges_sha256"] == c5["ranges_sha256"]
+
+
+def test_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """without --full: set-up, warm-up, the timed steps, the line -- no side leg, whatever the --no-* switches say; and
+    --dump-outputs writes what the last timed step left for every pattern (float64 s / e / count), the same files from
+    run to run, equal to the gathered counts and to the oracle-made golden hash of this pattern set"""
+    from benchmarks.legs.common import counts_sha256, golden_key, ranges_sha256
+    argv = ["--gpus", "1", "--log2n", "16", "--npat", "8192", "--steps", "3", "--warmup", "1", "--pattern-seed", "7"]
+    runs = []
+    for tag in ("a", "b"):
+        d = tmp_path / ("out_" + tag)
+        full = _bench(argv + ["--dump-outputs", str(d), "--dump-counts", str(tmp_path / (tag + ".npy"))], tmp_path, tag)
+        assert sorted(os.listdir(d)) == ["count.npy", "e.npy", "s.npy"]
+        runs.append((full, {k: np.load(str(d / (k + ".npy"))) for k in ("s", "e", "count")}))
+    line, out = runs[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert abs(line["value"] - 8192 * 32 / (line["ms_per_step"] / 1e3)) <= 1e-9 * line["value"]
+    for k in ("locate", "cpu_baseline", "early_exit", "rlfm", "rccl_1rank", "config5_g1", "wide", "pmc", "matches_golden"):
+        assert k not in line, k
+    assert line["roofline"].get("requested_lines") is None            # no census either
+    for k, a in out.items():
+        assert a.dtype == np.float64 and a.shape == (8192,) and (a == runs[1][1][k]).all(), k
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    assert (out["e"] - out["s"] == out["count"]).all() and (out["count"] >= 1).all()
+    assert (out["count"] == np.load(str(tmp_path / "a.npy"))).all()
+    with open(os.path.join(ROOT, "tests", "golden", "config5_counts.json")) as f:
+        gold = json.load(f)["entries"][golden_key("dna", 16, 7, 8192, 32)]
+    assert counts_sha256(out["count"].astype(np.int64)) == gold["counts_sha256"] == line["counts_sha256"]
+    assert ranges_sha256(out["s"].astype(np.int64), out["e"].astype(np.int64)) == gold["ranges_sha256"]

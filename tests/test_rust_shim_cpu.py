@@ -140,10 +140,50 @@ def test_the_overlay_covers_the_multi_pieces_backend():
     assert "+            rows: backend.match_rows(i, e, match_prefix_only)," in p
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="reference checkout not present")
+def patch_hunks():
+    """{file: [(old start, old length, new length, [old lines], number of new lines)]} of gpu-backend.patch"""
+    files, name, cur = {}, None, None
+    for ln in open(os.path.join(RUST, "gpu-backend.patch")).read().splitlines():
+        if ln.startswith("--- a/"):
+            name, cur = ln[6:].strip(), None
+            files[name] = []
+            continue
+        m = re.match(r"@@ -(\d+),(\d+) \+\d+,(\d+) @@", ln)
+        if m and name:
+            cur = [int(m.group(1)), int(m.group(2)), int(m.group(3)), [], 0]
+            files[name].append(cur)
+        elif cur is not None and not ln.startswith(("+++", "diff ", "index ")):
+            if ln[:1] in (" ", "-") or ln == "":
+                cur[3].append(ln[1:])
+            if ln[:1] in (" ", "+") or ln == "":
+                cur[4] += 1
+    return files
+
+
 def test_the_patch_applies_to_the_reference(tmp_path):
+    """every hunk's context + removed lines are the reference's lines at the hunk's own position (no offset, no fuzz):
+    hashed against tests/golden/patch_targets.json, which tests/golden/make_patch_targets.py made from the reference
+    crate -- and, where FM_INDEX_REFERENCE names a checkout of the reference, `patch --dry-run` on a copy of it as well"""
+    import hashlib
+    import json
     import shutil
-    shutil.copytree("/root/reference/src", tmp_path / "src")
+    with open(os.path.join(ROOT, "tests", "golden", "patch_targets.json")) as f:
+        gold = json.load(f)["files"]
+    hunks = patch_hunks()
+    assert set(hunks) == set(gold) == {"src/backend.rs", "src/lib.rs", "src/wrapper.rs"}
+    for name, hs in hunks.items():
+        assert len(hs) == len(gold[name]["hunks"]), name
+        end = 0
+        for (start, olen, nlen, old, nnew), g in zip(hs, gold[name]["hunks"]):
+            assert len(old) == olen and nnew == nlen, (name, start)          # the hunk header counts its own lines
+            assert start > end and start + olen - 1 <= gold[name]["lines"], (name, start)
+            end = start + olen - 1
+            assert (start, olen) == (g["start"], g["len"]), (name, start)
+            assert hashlib.sha256("\n".join(old).encode()).hexdigest() == g["sha256"], (name, start)
+    ref = os.environ.get("FM_INDEX_REFERENCE")           # a checkout of ajalab/fm-index, when there is one
+    if not ref:
+        return
+    shutil.copytree(os.path.join(ref, "src"), tmp_path / "src")
     p = subprocess.run(["patch", "-p1", "--dry-run", "-i", os.path.join(RUST, "gpu-backend.patch")],
                        cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     assert p.returncode == 0, p.stdout.decode()
