@@ -26,6 +26,8 @@ def main():
     ap.add_argument("--locate-patterns", type=int, default=1 << 17)
     ap.add_argument("--no-run-table", action="store_true")
     ap.add_argument("--narrow", action="store_true", help="the 32-bit engine (needs --log2n <= 31), for comparison")
+    ap.add_argument("--kmer-table", action="store_true", help="build with FMX_FLAG_KMER_TABLE (KMER=1 in the environment "
+                    "does the same); kmer_k and count_checksum in the output")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sweep-ep-blocks", default="", help="measurement build: count kernel ms per FMXW_EP_BLOCKS value "
                     "(and 'group' = the group-per-pattern kernel)")
@@ -37,7 +39,8 @@ def main():
     t0 = time.time()
     idx = F.RLFMIndexWithLocate.from_device_text(text.data_ptr(), n, 255, level=a.level,
                                                  force_wide=bool(a.log2n) and not a.narrow,
-                                                 walk_records=not a.no_run_table)
+                                                 walk_records=not a.no_run_table,
+                                                 kmer_table=a.kmer_table or os.environ.get("KMER") == "1")
     wall = time.time() - t0
     h = idx.handle()
     m, npat = a.m, a.npat
@@ -58,6 +61,7 @@ def main():
         torch.cuda.synchronize()
         kms.append(float(lib.fmx_last_kernel_ms(h)))
     count_steps = int(lib.fmx_last_steps(h))
+    count_checksum = int((s.sum() * 3 + e.sum()).item() & ((1 << 62) - 1))
     sweep = {}
     for v in [x for x in a.sweep_ep_blocks.split(",") if x]:
         if v == "group":
@@ -109,6 +113,7 @@ def main():
     cm, lm = min(kms), min(lms)
     print(json.dumps({
         "n": n, "wide": bool(idx.is_wide()), "runs": int(lib.fmx_num_runs(h)), "run_table": bool(idx.walk_records()),
+        "kmer_k": idx.kmer_k(), "count_checksum": count_checksum,
         "level": a.level, "index_bytes": idx.heap_size(), "build_ms": round(float(lib.fmx_build_ms(h)), 1),
         "build_wall_s": round(wall, 2),
         "count": {"patterns": npat, "m": m, "kernel_ms": round(cm, 4), "pattern_chars_per_s": npat * m / (cm / 1e3),

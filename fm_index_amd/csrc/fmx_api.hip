@@ -271,7 +271,11 @@ int fmx_walk_records(const fmx_index *idx) {
   return idx && (idx->is_wide ? (idx->wide.walk != nullptr || idx->wide.lfrun != nullptr)
                               : (idx->dev.walk != nullptr || idx->dev.lfrun != nullptr)) ? 1 : 0;
 }
-uint32_t fmx_kmer_k(const fmx_index *idx) { return idx && idx->dev.kmer ? idx->dev.kmer_k : 0; }
+uint32_t fmx_kmer_k(const fmx_index *idx) {
+  if (!idx) return 0;
+  if (idx->is_wide) return idx->wide.kmer ? idx->wide.kmer_k : 0;
+  return idx->dev.kmer ? idx->dev.kmer_k : 0;
+}
 double fmx_build_ms(const fmx_index *idx) { return idx ? idx->build_ms : 0.0; }
 
 void fmx_set_timing(fmx_index *idx, int enabled) {
@@ -1420,7 +1424,7 @@ const char *validate_loaded(const FileHeader &h, const FmxDev &d) {
   return nullptr;
 }
 const size_t kChunk = 64u << 20;
-const uint32_t kFileVersion = 10;   // 10: wide RLFM indexes (FmxWideDev::b / bp / lfrun); 9: FmxDev::walk (walk records: a presence flag only, rebuilt by fmx_load); 2: select hints every 64 ones (was 512); 3: positions of sparse vectors; 4: wavelet select hints; 5: dense select blocks; 6: pointer fields written as presence flags, fields validated on load; 7: select blocks of 8 / 16 / 32 / 64 ones by density; 8: text-order sampling (phase pieces)
+const uint32_t kFileVersion = 11;   // 11: k-mer start table of wide indexes (FmxWideDev::kmer / kmer_k / kmer_bits); 10: wide RLFM indexes (FmxWideDev::b / bp / lfrun); 9: FmxDev::walk (walk records: a presence flag only, rebuilt by fmx_load); 2: select hints every 64 ones (was 512); 3: positions of sparse vectors; 4: wavelet select hints; 5: dense select blocks; 6: pointer fields written as presence flags, fields validated on load; 7: select blocks of 8 / 16 / 32 / 64 ones by density; 8: text-order sampling (phase pieces)
 }  // namespace
 
 // wide indexes (n >= 2^32 - 16): header (dev_struct_bytes carries kWideMark) | FmxWideDev with presence flags for
@@ -1466,6 +1470,9 @@ WideBlobs wide_blobs(FmxWideDev &w, uint64_t nsamples) {
     }
   }
   if (w.kind == FMX_KIND_MULTI) { b.field[b.n] = (const void **)&w.doc; b.bytes[b.n++] = w.doc_count * 4ull; }
+  if (w.kmer) {   // (load_wide has checked kmer_bits * kmer_k <= 24)
+    b.field[b.n] = (const void **)&w.kmer; b.bytes[b.n++] = (1ull << (w.kmer_bits * w.kmer_k)) * sizeof(FmxWideKmer);
+  }
   return b;
 }
 }  // namespace
@@ -1591,6 +1598,19 @@ static int load_wide(FILE *f, const FileHeader &h, int device, fmx_index *idx) {
           v.nrec != (uint32_t)((slen >> (fmt == 3 ? 8 : 7)) + 1u) || w.sb_shift < (fmt == 3 ? 8u : 7u))
         bad = "level fields";
     }
+  }
+  if (!bad) {
+    // k-mer start table: the presence flag is exactly 0 or 1; with it, the fields are the builder's (u8 symbols, RLFM or
+    // one wavelet level, bits = ceil(log2(max_character)), k <= 16 symbols of the group's two-per-lane read, at most 2^24
+    // entries, at most n / 32 of them) -- the entry count sizes the blob, which must then be in the file; without it, both are 0
+    uint32_t kbits = 1;
+    while ((1u << kbits) < (uint32_t)h.max_character && kbits < 26) kbits++;
+    if ((uintptr_t)w.kmer > 1) bad = "k-mer table flag";
+    else if (w.kmer ? (w.kmer_k == 0 || w.kmer_bits == 0 || w.kmer_bits > 8 || w.kmer_k > 16 || w.kmer_bits != kbits ||
+                       w.kmer_bits * w.kmer_k > 24 || (1ull << (w.kmer_bits * w.kmer_k)) > h.n / 32u || h.sym_bytes != 1 ||
+                       !(rl || !w.generic || w.nlevels == 1))
+                    : (w.kmer_k != 0 || w.kmer_bits != 0))
+      bad = "k-mer table";
   }
   if (!bad && rl) {
     const FmxWideBits *v[2] = {&w.b, &w.bp};

@@ -3003,6 +3003,35 @@ static int build_rlfm_wide(fmx_index *idx, T *d_L, uint64_t n, uint32_t L, DevPo
   return FMX_OK;
 }
 
+// opt-in k-mer start table of a wide index (FMX_FLAG_KMER_TABLE; FmxWideDev::kmer), built once the rank structures
+// exist.  The 32-bit builder's rule: u8 symbols, max_character >= 1, n >= 2; RLFM always, FM / multi-pieces when the
+// BWT has one wavelet level.  16-byte entries, so 2^(bits k) <= n / 32 keeps the table within n / 2 bytes.
+template <typename T>
+static int build_wide_kmer(fmx_index *idx) {
+  FmxWideDev &w = idx->wide;
+  w.kmer = nullptr; w.kmer_k = 0; w.kmer_bits = 0;
+  const uint32_t maxc = w.max_character;
+  if (!(idx->flags & FMX_FLAG_KMER_TABLE) || sizeof(T) != 1 || maxc < 1 || w.n < 2 ||
+      !(idx->kind == FMX_KIND_RLFM || !w.generic || w.nlevels == 1))
+    return FMX_OK;
+  uint32_t bits = 1;
+  while ((1u << bits) < maxc) bits++;               // symbol c is coded c - 1 in 0..maxc-1
+  uint32_t kk = 24u / bits;                          // <= 2^24 entries (256 MiB)
+  if (kk > 16) kk = 16;                              // two symbols per lane of the 8-lane group
+  while (kk > 0 && (1ull << (bits * kk)) > w.n / 32u) kk--;   // table <= n/2 bytes
+  if (kk < 2) return FMX_OK;
+  FmxWideKmer *d_tab;
+  const uint64_t tab_bytes = (1ull << (bits * kk)) * sizeof(FmxWideKmer);
+  FMX_HIP(fmx_dev_malloc((void **)&d_tab, tab_bytes));
+  if (int rc = keep(idx, d_tab, tab_bytes)) return rc;
+  if (int rc = fmxw_launch_kmer_build(idx, d_tab, kk, bits, 0)) return rc;
+  FMX_HIP(hipDeviceSynchronize());
+  w.kmer = d_tab;
+  w.kmer_k = kk;
+  w.kmer_bits = bits;
+  return FMX_OK;
+}
+
 template <typename T>
 static int build_wide_t(fmx_index *idx, const T *d_text) {
   auto t0 = std::chrono::steady_clock::now();
@@ -3303,6 +3332,8 @@ static int build_wide_t(fmx_index *idx, const T *d_text) {
     if (int rc = build_rlfm_wide<T>(idx, d_bwt, n, L, pool)) return rc;
     idx->is_wide = 1;
     mark("rlfm");
+    if (int rc = build_wide_kmer<T>(idx)) return rc;
+    mark("k-mer table");
     idx->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return FMX_OK;
   }
@@ -3323,6 +3354,8 @@ static int build_wide_t(fmx_index *idx, const T *d_text) {
     FMX_HIP(hipDeviceSynchronize());
     idx->is_wide = 1;
     mark("levels");
+    if (int rc = build_wide_kmer<T>(idx)) return rc;
+    mark("k-mer table");
     idx->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return FMX_OK;
   }
@@ -3359,6 +3392,8 @@ static int build_wide_t(fmx_index *idx, const T *d_text) {
   w.sb_shift = sb_shift;
   idx->is_wide = 1;
   mark("records");
+  if (int rc = build_wide_kmer<T>(idx)) return rc;
+  mark("k-mer table");
   idx->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return FMX_OK;
 }

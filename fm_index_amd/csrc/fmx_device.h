@@ -84,6 +84,39 @@ __device__ __forceinline__ uint32_t fmx_group_min(uint32_t v) {
   return v;
 }
 
+// index into the k-mer start table (FMX_FLAG_KMER_TABLE; both engines): the symbol consumed FIRST (the
+// pattern's last) sits in the top bits, each coded c - 1.
+// the group's lanes read the last `kk` (<= 16) symbols of the pattern (two per lane) and combine
+// them; returns false when one of them is 0 or > max_character (then the stepwise path decides)
+__device__ __forceinline__ bool fmx_kmer_code(const uint8_t *__restrict__ pat, uint64_t pend, uint32_t kk,
+                                              uint32_t bits, uint32_t max_character, uint32_t g,
+                                              uint32_t &code) {
+  uint32_t part = 0, bad = 0;
+#pragma unroll
+  for (uint32_t h = 0; h < 2; h++) {
+    const uint32_t t = g + 8u * h;                      // t-th symbol from the back
+    if (t < kk) {
+      const uint32_t cc = pat[pend - 1u - t];
+      bad |= (uint32_t)((cc - 1u) >= max_character);
+      part |= ((cc - 1u) & ((1u << bits) - 1u)) << (bits * (kk - 1u - t));
+    }
+  }
+  code = fmx_group_sum(part);                           // disjoint bit fields: sum == or
+  return fmx_group_sum(bad) == 0u;
+}
+// the same code computed by ONE lane from its own reads (the endpoint-per-lane kernels)
+__device__ __forceinline__ bool fmx_kmer_code_lane(const uint8_t *__restrict__ pat, uint64_t pend, uint32_t kk,
+                                                   uint32_t bits, uint32_t max_character, uint32_t &code) {
+  uint32_t bad = 0;
+  code = 0;
+  for (uint32_t t = 0; t < kk; t++) {                     // t-th symbol from the back
+    const uint32_t cc = pat[pend - 1u - t];
+    bad |= (uint32_t)((cc - 1u) >= max_character);
+    code |= ((cc - 1u) & ((1u << bits) - 1u)) << (bits * (kk - 1u - t));
+  }
+  return bad == 0u;
+}
+
 // value of lane (4 * (lane / 4) + q) for the four lanes of a quad (DPP quad_perm [q,q,q,q])
 template <int QQ>
 __device__ __forceinline__ uint32_t fmx_quad_bcast_c(uint32_t v) {

@@ -180,6 +180,7 @@ struct FmxWideBits {
 #define FMXW_BITS_SB_SHIFT_TEST 1u  // FMX_FLAG_FORCE_WIDE
 #define FMXW_PHASE_SB_SHIFT 24u     // phase pieces per superblock (<= 96 rows each: < 2^31 rows)
 #define FMXW_PHASE_SB_SHIFT_TEST 3u // FMX_FLAG_FORCE_WIDE
+struct alignas(16) FmxWideKmer { uint64_t s, e; };   // one entry of the wide k-mer start table
 struct FmxWideDev {  // passed BY VALUE to the wide kernels
   const uint4 *rec;          // one 3-bit level (max_character <= 7): n / 256 + 1 records (row n is addressable)
   const uint64_t *base;      // ... [nsb][8], cs[] folded in
@@ -225,8 +226,15 @@ struct FmxWideDev {  // passed BY VALUE to the wide kernels
   // k-th end marker in L order, first_row = sa_idx_first_text (multi_pieces.rs:21-22, 57-85), as FmxDev::doc / first_row
   const uint32_t *doc;
   uint64_t doc_count, first_row;
+  // FMX_FLAG_KMER_TABLE on the wide engine (u8 symbols; RLFM always, FM / multi-pieces over one wavelet level): entry
+  // `code` (fmx_kmer_code) = the (s, e) SearchWrapper::search leaves for that k-mer from (0, n), early exit included,
+  // as FmxDev::kmer -- 16 bytes per entry, one dwordx4 load.  k = min(24 / bits, 16), reduced while
+  // 2^(bits k) > n / 32: the table never exceeds n / 2 bytes (nor 256 MiB); no table when k < 2.
+  const FmxWideKmer *kmer;
+  uint32_t kmer_k;           // symbols per entry (0 = no table)
+  uint32_t kmer_bits;        // bits per symbol in the table index (symbol c is coded c - 1)
 };
-#define FMXW_WALK_SB_SHIFT 24u      // records per walk superblock: 2^24 x 112 rows < 2^31, so relative counters fit 32 bits
+#define FMXW_WALK_SB_SHIFT 24u     // records per walk superblock: 2^24 x 112 rows < 2^31, so relative counters fit 32 bits
 #define FMXW_WALK_SB_SHIFT_TEST 5u  // FMX_FLAG_FORCE_WIDE: 32 records, so that a small text has many superblocks
 
 struct fmx_index {
@@ -322,6 +330,8 @@ int fmxw_launch_match(const fmx_index *idx, const uint64_t *d_s, const uint64_t 
                       const uint64_t *d_off, uint64_t *d_out, hipStream_t st);   // d_off == NULL: counts, else rows
 int fmxw_verify_sa(const fmx_index *idx, uint64_t *violations);
 int fmxw_launch_compute_K(const FmxWideDev &w, uint64_t *d_K);   // generic wide index: K[c] = cs[c] - rank chain of c at 0
+// fills table[code] for every k-mer code of a wide index (FMX_FLAG_KMER_TABLE; idx->wide's rank structures must be complete)
+int fmxw_launch_kmer_build(const fmx_index *idx, FmxWideKmer *d_table, uint32_t k, uint32_t bits, hipStream_t st);
 // rows s[k] + j of every interval, 64 bits each (wrapper.rs:203-217), written to out[off[k] + j]
 int fmx_launch_expand64(const uint64_t *d_s, const uint64_t *d_e, const uint64_t *d_off, uint64_t npat,
                         uint64_t *d_out, uint64_t total, uint64_t n, uint32_t *status, hipStream_t st);

@@ -35,26 +35,8 @@ static inline unsigned fmx_grid_for_groups(uint64_t units) {
 // ---------------------------------------------------------------------------
 // k-mer start table (FMX_FLAG_KMER_TABLE).  Entry `code` = the (s, e) SearchWrapper::search
 // leaves for the k-mer, early exit included, so a lookup replaces the first k steps exactly.
-// code: the symbol consumed FIRST (the pattern's last) sits in the top bits, each coded c - 1.
+// code: fmx_kmer_code / fmx_kmer_code_lane (fmx_device.h, shared with the wide engine).
 // ---------------------------------------------------------------------------
-// the group's lanes read the last `kk` (<= 16) symbols of the pattern (two per lane) and combine
-// them; returns false when one of them is 0 or > max_character (then the stepwise path decides)
-__device__ __forceinline__ bool fmx_kmer_code(const uint8_t *__restrict__ pat, uint64_t pend, uint32_t kk,
-                                              uint32_t bits, uint32_t max_character, uint32_t g,
-                                              uint32_t &code) {
-  uint32_t part = 0, bad = 0;
-#pragma unroll
-  for (uint32_t h = 0; h < 2; h++) {
-    const uint32_t t = g + 8u * h;                      // t-th symbol from the back
-    if (t < kk) {
-      const uint32_t cc = pat[pend - 1u - t];
-      bad |= (uint32_t)((cc - 1u) >= max_character);
-      part |= ((cc - 1u) & ((1u << bits) - 1u)) << (bits * (kk - 1u - t));
-    }
-  }
-  code = fmx_group_sum(part);                           // disjoint bit fields: sum == or
-  return fmx_group_sum(bad) == 0u;
-}
 template <int KIND>
 __global__ __launch_bounds__(FMX_BLOCK) void fmx_kmer_build_kernel(FmxDev ix, uint2 *__restrict__ table,
                                                                     uint32_t kk, uint32_t bits) {
@@ -488,17 +470,6 @@ __global__ __launch_bounds__(FMX_BLOCK) void fmx_count_pair_kernel(
 // SM = 1 (stored positions) or 2 (select blocks); indexes whose B / B' fall into neither class stay
 // on fmx_count_kernel<FMX_KIND_RLFM>.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ bool fmx_kmer_code_lane(const uint8_t *__restrict__ pat, uint64_t pend, uint32_t kk,
-                                                   uint32_t bits, uint32_t max_character, uint32_t &code) {
-  uint32_t bad = 0;
-  code = 0;
-  for (uint32_t t = 0; t < kk; t++) {                     // t-th symbol from the back
-    const uint32_t cc = pat[pend - 1u - t];
-    bad |= (uint32_t)((cc - 1u) >= max_character);
-    code |= ((cc - 1u) & ((1u << bits) - 1u)) << (bits * (kk - 1u - t));
-  }
-  return bad == 0u;
-}
 template <int KIND, int NL, int SM, bool KM>
 __global__ __launch_bounds__(FMX_BLOCK) void fmx_count_ep_kernel(
     FmxDev ix, const void *__restrict__ pat, const uint64_t *__restrict__ off, uint64_t npat,

@@ -15,6 +15,9 @@
 // (fmxw_g_walk_text_ep_kernel; RLFM with the run table: fmxw_r_walk_text_kernel / fmxw_r_walk_kernel), a group per walk for
 // row-order samples; the group-per-pattern / four-walks-per-group kernels of round 4 stay for the measurement build's A/B
 // (FMXW_R_COUNT_GROUP=1).  Third part: RLFMIndex (B / B' with 64-bit superblock bases, S on the generic levels).
+// FMX_FLAG_KMER_TABLE (round 7): the KM = true instantiations of fmxw_count_kernel / fmxw_g_count_ep_kernel take a fresh
+// pattern's first kmer_k steps from one 16-byte entry of FmxWideDev::kmer (built by fmxw_kmer_build_kernel /
+// fmxw_g_kmer_build_kernel); KM = false is the code of the indexes without a table, unchanged.
 #include "fmx_device.h"
 
 #define FMXW_BLOCK 256
@@ -133,7 +136,10 @@ __device__ __forceinline__ uint64_t fmxw_get_sa_walk(const FmxWideDev &w, uint64
 
 // SearchWrapper::search for a batch (wrapper.rs:103-124): a group per pattern.  Per step the two record loads and
 // the NEXT pattern symbol are requested together and waited for once; the base of the step's symbol comes from LDS.
-template <bool LDSB>
+// KM: the index has a k-mer start table (FmxWideDev::kmer) -- a fresh search from (0, n) over at least kmer_k symbols
+// takes its first kmer_k steps from ONE 16-byte entry; the entry is what those steps leave, early exit included, so the
+// results are those of the KM = false kernel bit for bit.
+template <bool LDSB, bool KM>
 __global__ __launch_bounds__(FMXW_BLOCK) void fmxw_count_kernel(
     FmxWideDev w, const uint8_t *__restrict__ pat, const uint64_t *__restrict__ off, uint64_t npat,
     const uint64_t *__restrict__ s0e0, uint64_t *__restrict__ out_s, uint64_t *__restrict__ out_e,
@@ -160,6 +166,20 @@ __global__ __launch_bounds__(FMXW_BLOCK) void fmxw_count_kernel(
       if (g == 0) atomicOr(w.status, 1u << FMX_ERR_ARG);
       s = 0; e = 0; j = 0;
     }
+    if constexpr (KM) {
+      if (!s0e0 && j >= w.kmer_k) {                 // the first kmer_k steps from the table (a refused pattern has j = 0)
+        uint32_t code;
+        if (fmx_kmer_code(pat, pbeg + j, w.kmer_k, w.kmer_bits, w.max_character, g, code)) {
+          FMX_CHECK(code < (1u << (w.kmer_bits * w.kmer_k)));
+          FMX_TOUCH_G0N(g, &w.kmer[code]);
+          const FmxWideKmer se = w.kmer[code];
+          s = se.s;
+          e = se.e;
+          j = se.s == se.e ? 0u : j - w.kmer_k;     // empty already: the reference's break   wrapper.rs:111-113
+          nsteps += w.kmer_k;
+        }                                           // a 0 or a symbol > max_character among them: the stepwise path decides
+      }
+    }
     uint32_t c = j ? pat[pbeg + j - 1] : 0u;        // for c in pattern.iter().rev()          wrapper.rs:108
     while (j) {
       if (c > w.max_character) {                    // reference: panic on cs[c]
@@ -185,6 +205,33 @@ __global__ __launch_bounds__(FMXW_BLOCK) void fmxw_count_kernel(
     }
   }
   if (steps_out && g == 0 && nsteps) atomicAdd((unsigned long long *)steps_out, (unsigned long long)nsteps);
+}
+
+// k-mer start table of a one-level index (FMX_FLAG_KMER_TABLE; the wide twin of fmx_kmer_build_kernel): a group per
+// code runs SearchWrapper::search from (0, n) over the code's symbols, the break included -- fmxw_lf_map2 with the
+// bases of FMXW_BASES.  Codes that hold a symbol above max_character get (0, 0): fmx_kmer_code never produces them.
+template <bool LDSB>
+__global__ __launch_bounds__(FMXW_BLOCK) void fmxw_kmer_build_kernel(FmxWideDev w, FmxWideKmer *__restrict__ table,
+                                                                      uint32_t kk, uint32_t bits) {
+  FMXW_BASES(w, LDSB);
+  const uint32_t g = threadIdx.x & (FMX_GROUP - 1);
+  const uint64_t gid = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / FMX_GROUP;
+  const uint64_t ngroups = ((uint64_t)gridDim.x * blockDim.x) / FMX_GROUP;
+  const uint64_t ncodes = 1ull << (bits * kk);
+  for (uint64_t code = gid; code < ncodes; code += ngroups) {
+    uint64_t s = 0, e = w.n;
+    for (uint32_t t = 0; t < kk; t++) {
+      const uint32_t c = (uint32_t)((code >> (bits * (kk - 1u - t))) & ((1u << bits) - 1u)) + 1u;
+      if (c > w.max_character) { s = 0; e = 0; break; }     // never looked up
+      FMX_CHECK((e >> 8) < w.n / 256u + 1u && (s >> w.sb_shift) < w.nsb && (e >> w.sb_shift) < w.nsb);
+      const uint4 pa = w.rec[(size_t)(s >> 8) * 8u + g], pb = w.rec[(size_t)(e >> 8) * 8u + g];
+      const uint64_t ba = base_at(s, c), bb = base_at(e, c);
+      s = ba + fmx_group_sum(fmx_piece_rank<3>(pa, (uint32_t)s & 255u, c, g));      // wrapper.rs:109
+      e = bb + fmx_group_sum(fmx_piece_rank<3>(pb, (uint32_t)e & 255u, c, g));      // wrapper.rs:110
+      if (s == e) break;                                    // wrapper.rs:111-113
+    }
+    if (g == 0) table[code] = FmxWideKmer{s, e};
+  }
 }
 
 // get_sa for a batch of rows (fm_index.rs:127-140; sample.rs:46-60).  `io` holds the row on entry and the position
@@ -930,8 +977,38 @@ __global__ __launch_bounds__(64) void fmxw_g_compute_K_kernel(FmxWideDev w, uint
   if (g == 0) K[c] = w.cs[c] - sc;
 }
 
+// k-mer start table of a generic index (FMX_FLAG_KMER_TABLE: FM / multi-pieces over one wavelet level, RLFM): a group
+// per code, SearchWrapper::search from (0, n) with the break, through the lf_map2 of the group kernels below (K[c] + rank
+// chain; a table symbol is never 0, so a multi-pieces index needs no end-marker rule) or fmxw_r_lf_map2_pair
+template <bool GLDS, int KD>
+__global__ __launch_bounds__(FMXW_BLOCK) void fmxw_g_kmer_build_kernel(FmxWideDev w, FmxWideKmer *__restrict__ table,
+                                                                        uint32_t kk, uint32_t bits) {
+  FMXW_GBASES(w, GLDS);
+  const uint32_t g = threadIdx.x & (FMX_GROUP - 1);
+  const uint64_t gid = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / FMX_GROUP;
+  const uint64_t ngroups = ((uint64_t)gridDim.x * blockDim.x) / FMX_GROUP;
+  const uint64_t ncodes = 1ull << (bits * kk);
+  for (uint64_t code = gid; code < ncodes; code += ngroups) {
+    uint64_t s = 0, e = w.n;
+    for (uint32_t t = 0; t < kk; t++) {
+      const uint32_t c = (uint32_t)((code >> (bits * (kk - 1u - t))) & ((1u << bits) - 1u)) + 1u;
+      if (c > w.max_character) { s = 0; e = 0; break; }     // never looked up
+      if constexpr (KD == FMX_KIND_RLFM) {
+        fmxw_r_lf_map2_pair(w, gbase, gk, c, s, e, g);      // rlfmi.rs:135-143
+      } else {
+        const uint64_t kc = gk(c);
+        s = kc + fmxw_g_chain(w, gbase, c, s, g);           // wrapper.rs:109
+        e = kc + fmxw_g_chain(w, gbase, c, e, g);           // wrapper.rs:110
+      }
+      if (s == e) break;                                    // wrapper.rs:111-113
+    }
+    if (g == 0) table[code] = FmxWideKmer{s, e};
+  }
+}
+
 // SearchWrapper::search for a batch (wrapper.rs:103-124): a group per pattern; per level the records of both
-// interval ends are requested together, the next pattern symbol with the first level's
+// interval ends are requested together, the next pattern symbol with the first level's.  (Stepwise only: it never reads
+// the k-mer start table, the launcher picks it when the endpoint kernel cannot run.)
 template <bool GLDS, int KD>
 __global__ __launch_bounds__(FMXW_BLOCK) void fmxw_g_count_kernel(
     FmxWideDev w, const void *__restrict__ pat, const uint64_t *__restrict__ off, uint64_t npat,
@@ -1394,7 +1471,10 @@ __device__ __forceinline__ uint64_t fmxw_g_ep_lf_map(const FmxWideDev &w, const 
 // SearchWrapper::search for a batch (wrapper.rs:103-124) on a wide generic index (KD: FM, RLFM, multi-pieces), an interval endpoint per lane.  Pattern
 // slots are dealt to the groups first (slot = pair * ngroups + group), so a batch smaller than the grid has one live
 // lane pair per group and a round costs one record per level.
-template <bool GLDS, int KD>
+// KM: the index has a k-mer start table -- on a fresh search from (0, n) each lane of a pair computes the code of the
+// last kmer_k symbols from its own reads and loads ITS 8-byte half of the entry; an empty entry ends the pattern on
+// that round (the reference's break), so the results are those of the KM = false kernel bit for bit.
+template <bool GLDS, int KD, bool KM>
 __global__ __launch_bounds__(FMXW_BLOCK) void fmxw_g_count_ep_kernel(
     FmxWideDev w, const void *__restrict__ pat, const uint64_t *__restrict__ off, uint64_t npat,
     const uint64_t *__restrict__ s0e0, uint64_t *__restrict__ out_s, uint64_t *__restrict__ out_e,
@@ -1422,6 +1502,21 @@ __global__ __launch_bounds__(FMXW_BLOCK) void fmxw_g_count_ep_kernel(
         bad |= mine > w.n || other > w.n;             // not a range of this index
       } else {
         pos = is_e ? w.n : 0ull;                      // SearchIndexWrapper::search: (0, len)   wrapper.rs:41
+        if constexpr (KM) {
+          if (!bad && j >= w.kmer_k) {                // the first kmer_k steps from the table (u8 symbols)
+            uint32_t code;
+            if (fmx_kmer_code_lane((const uint8_t *)pat, pbeg + j, w.kmer_k, w.kmer_bits, w.max_character, code)) {
+              FMX_CHECK(code < (1u << (w.kmer_bits * w.kmer_k)));
+              const uint64_t *half = (const uint64_t *)(w.kmer + code) + is_e;
+              FMX_TOUCH(half);
+              pos = *half;
+              // the pair's other half (both lanes of a pair take the same branches, so both are here)
+              const uint64_t oth = (uint64_t)fmx_dpp_xor1((uint32_t)pos) | ((uint64_t)fmx_dpp_xor1((uint32_t)(pos >> 32)) << 32);
+              j = pos == oth ? 0ull : j - w.kmer_k;   // empty already: the reference's break   wrapper.rs:111-113
+              nsteps += is_e ? 0u : w.kmer_k;
+            }                                         // a 0 or a symbol > max_character among them: the stepwise path decides
+          }
+        }
       }
       if (bad) {                                      // refuse, do not read
         if (is_e) atomicOr(w.status, 1u << FMX_ERR_ARG);
@@ -1822,8 +1917,12 @@ int fmxw_launch_count(const fmx_index *idx, const void *d_pat, const uint64_t *d
   fmxw_time_begin(idx, st);
   if (w.generic) {
 #define FMXW_GCNT(GLDS, RL)                                                                                        \
-  hipLaunchKernelGGL((fmxw_g_count_kernel<GLDS, RL>), dim3(fmxw_grid(npat)), dim3(FMXW_BLOCK), 0, st, w, d_pat,       \
+  hipLaunchKernelGGL((fmxw_g_count_kernel<GLDS, RL>), dim3(fmxw_grid(npat)), dim3(FMXW_BLOCK), 0, st, wg, d_pat,      \
                      d_off, npat, d_s0e0, d_s, d_e, d_cnt, idx->timing == 1 ? idx->d_steps : nullptr)
+    // the group-per-pattern kernel (sb_shift > 31, or the measurement build's A/B switch) is stepwise: its launch
+    // passes no k-mer table -- the entries are what its steps compute, so the results are the same either way
+    FmxWideDev wg = w;
+    wg.kmer = nullptr; wg.kmer_k = 0; wg.kmer_bits = 0;
     const bool r_group = fmxw_env_group();
     if (w.sb_shift <= 31u && !r_group) {              // an interval endpoint per lane (32 patterns per block at a time)
       uint64_t eb = (npat + FMXW_BLOCK / 8 - 1) / (FMXW_BLOCK / 8);
@@ -1833,8 +1932,14 @@ int fmxw_launch_count(const fmx_index *idx, const void *d_pat, const uint64_t *d
 #endif
       if (eb > cap) eb = cap;
 #define FMXW_RCNT(GLDS, KD)                                                                                         \
-  hipLaunchKernelGGL((fmxw_g_count_ep_kernel<GLDS, KD>), dim3((unsigned)eb), dim3(FMXW_BLOCK), 0, st, w, d_pat, d_off,  \
-                     npat, d_s0e0, d_s, d_e, d_cnt, idx->timing == 1 ? idx->d_steps : nullptr)
+  do {                                                                                                              \
+    if (w.kmer)                                                                                                     \
+      hipLaunchKernelGGL((fmxw_g_count_ep_kernel<GLDS, KD, true>), dim3((unsigned)eb), dim3(FMXW_BLOCK), 0, st, w,   \
+                         d_pat, d_off, npat, d_s0e0, d_s, d_e, d_cnt, idx->timing == 1 ? idx->d_steps : nullptr);   \
+    else                                                                                                            \
+      hipLaunchKernelGGL((fmxw_g_count_ep_kernel<GLDS, KD, false>), dim3((unsigned)eb), dim3(FMXW_BLOCK), 0, st, w,  \
+                         d_pat, d_off, npat, d_s0e0, d_s, d_e, d_cnt, idx->timing == 1 ? idx->d_steps : nullptr);   \
+  } while (0)
       if (w.kind == FMX_KIND_RLFM) { if (w.nsb <= FMXW_GLDS_SB) FMXW_RCNT(true, FMX_KIND_RLFM); else FMXW_RCNT(false, FMX_KIND_RLFM); }
       else if (w.kind == FMX_KIND_MULTI) { if (w.nsb <= FMXW_GLDS_SB) FMXW_RCNT(true, FMX_KIND_MULTI); else FMXW_RCNT(false, FMX_KIND_MULTI); }
       else if (w.nsb <= FMXW_GLDS_SB) FMXW_RCNT(true, FMX_KIND_FM); else FMXW_RCNT(false, FMX_KIND_FM);
@@ -1848,11 +1953,30 @@ int fmxw_launch_count(const fmx_index *idx, const void *d_pat, const uint64_t *d
   }
   // group per pattern, one pattern per group at a time: two patterns per group in flight, or one record load for
   // both ends of a narrow interval, measured slower (0.75-0.80 ms against 0.70 ms, benchmarks/gpu/wide_tune.sh)
-#define FMXW_CNT(LDSB)                                                                                             \
-  hipLaunchKernelGGL(fmxw_count_kernel<LDSB>, dim3(fmxw_grid(npat)), dim3(FMXW_BLOCK), 0, st, w, (const uint8_t *)d_pat, \
-                     d_off, npat, d_s0e0, d_s, d_e, d_cnt, idx->timing == 1 ? idx->d_steps : nullptr)
-  if (w.nsb <= FMXW_LDS_SB) FMXW_CNT(true); else FMXW_CNT(false);
+#define FMXW_CNT(LDSB, KM)                                                                                         \
+  hipLaunchKernelGGL((fmxw_count_kernel<LDSB, KM>), dim3(fmxw_grid(npat)), dim3(FMXW_BLOCK), 0, st, w,               \
+                     (const uint8_t *)d_pat, d_off, npat, d_s0e0, d_s, d_e, d_cnt, idx->timing == 1 ? idx->d_steps : nullptr)
+  if (w.kmer) { if (w.nsb <= FMXW_LDS_SB) FMXW_CNT(true, true); else FMXW_CNT(false, true); }
+  else if (w.nsb <= FMXW_LDS_SB) FMXW_CNT(true, false); else FMXW_CNT(false, false);
   fmxw_time_end(idx, st);
+  FMX_HIP(hipGetLastError());
+  return FMX_OK;
+}
+
+// fills table[code] for every k-mer code of a wide index (FMX_FLAG_KMER_TABLE; the rank structures must be complete)
+int fmxw_launch_kmer_build(const fmx_index *idx, FmxWideKmer *d_table, uint32_t k, uint32_t bits, hipStream_t st) {
+  const FmxWideDev w = idx->wide;
+  const dim3 grid(fmxw_grid(1ull << (bits * k))), block(FMXW_BLOCK);
+#define FMXW_GKMB(KD)                                                                                              \
+  do {                                                                                                             \
+    if (w.nsb <= FMXW_GLDS_SB) hipLaunchKernelGGL((fmxw_g_kmer_build_kernel<true, KD>), grid, block, 0, st, w, d_table, k, bits);  \
+    else hipLaunchKernelGGL((fmxw_g_kmer_build_kernel<false, KD>), grid, block, 0, st, w, d_table, k, bits);        \
+  } while (0)
+  if (!w.generic) {
+    if (w.nsb <= FMXW_LDS_SB) hipLaunchKernelGGL(fmxw_kmer_build_kernel<true>, grid, block, 0, st, w, d_table, k, bits);
+    else hipLaunchKernelGGL(fmxw_kmer_build_kernel<false>, grid, block, 0, st, w, d_table, k, bits);
+  } else if (w.kind == FMX_KIND_RLFM) FMXW_GKMB(FMX_KIND_RLFM);
+  else FMXW_GKMB(FMX_KIND_FM);                      // multi-pieces: lf_map2 of a symbol >= 1 is the FM index's
   FMX_HIP(hipGetLastError());
   return FMX_OK;
 }

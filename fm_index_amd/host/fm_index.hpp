@@ -85,7 +85,8 @@ class Search {  // frontend.rs:70-84
 class Index {
  public:
   // `flags`: FMX_FLAG_PLAIN vetoes the count accelerators a DNA-like FM index of 2^24+ symbols gets by default (round 6);
-  // FMX_FLAG_PAIR_INDEX | FMX_FLAG_KMER_TABLE ask for them by name
+  // FMX_FLAG_PAIR_INDEX | FMX_FLAG_KMER_TABLE ask for them by name (the flags go to fmx_build as given, so a text of
+  // 2^32 - 16 symbols or more -- or FMX_FLAG_FORCE_WIDE -- gets the 64-bit engine's k-mer table the same way)
   Index(const Text &text, uint32_t kind, uint32_t level, int device = 0, uint32_t flags = 0) {
     check(fmx_build(text.text().data(), text.text().size(), 1, text.max_character(), kind, level, flags,
                     device, &h_));

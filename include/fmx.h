@@ -17,8 +17,9 @@
  *    positions and samples) for every kind, with or without locate (u8 / u16 / u32 symbols, max_character < 2^26;
  *    FMX_KIND_FM over u8 with max_character <= 7 -- DNA -- has the faster one-level kernels): every entry point
  *    works on it (build, count, locate, offsets, the trait calls, piece ids and match rows of a multi-pieces index,
- *    extract, save / load, the exports -- the samples through fmx_export_sa_samples64) except fmx_export_sa and
- *    the opt-in accelerators (flags ignored).
+ *    extract, save / load, the exports -- the samples through fmx_export_sa_samples64) except fmx_export_sa.  Of the
+ *    opt-in accelerators it honours FMX_FLAG_KMER_TABLE (below); FMX_FLAG_PAIR_INDEX is still ignored there, and the
+ *    default index of a text that long gets neither (the table is by request only).
  *  - symbols are `sym_bytes` wide: Character = u8 / u16 / u32 / u64 (character.rs:38-42) =
  *    1 / 2 / 4 / 8.  u64 texts are narrowed to u32 at build time (fmx_build on the host, fmx_build_dev by a
  *    kernel), u64 patterns by the host-pointer entry points; the *_dev query entry points take symbols of
@@ -86,7 +87,12 @@ typedef struct fmx_index fmx_index;
  * pair the reference's break would have left.  Patterns shorter than k, patterns whose last k
  * symbols contain 0 or an out-of-range symbol, and refinements from a given (s, e) take the
  * stepwise path.  Ignored when not applicable (wide symbols, texts too short for k >= 2, FM over
- * larger alphabets where the lookup costs more than the steps it replaces). */
+ * larger alphabets where the lookup costs more than the steps it replaces).
+ * The WIDE engine (len >= 2^32 - 16) honours the flag under the same rule: its entries are 16 bytes
+ * -- (s, e) as two uint64_t, one lookup --, k = min(floor(24 / bits), 16) reduced while
+ * 2^(bits k) > len / 32, so the table again never exceeds len/2 bytes (nor 256 MiB): k = 12 for DNA
+ * and 3 for a byte-alphabet RLFM index there.  The table is part of fmx_index_bytes(), of index
+ * files and of fmx_replicate()'s copies. */
 #define FMX_FLAG_KMER_TABLE 4u
 /* Which rows carry a suffix-array sample (levels 1..4; get_sa() returns SA[i] either way, and
  * fmx_export_sa_samples() always yields the reference's samples SA[k << level], sample.rs:33-37):
