@@ -7,7 +7,8 @@ load for both ends of a narrow interval; FMXW_WALKS: walks per group; FMXW_SB_SH
     python benchmarks/gpu/wide_tune.py LOG2N [extra]      n = 2^LOG2N + extra; n < 2^32 - 16 is built with force_wide
 
 Environment: NARROW=1 builds the 32-bit engine instead; KMER=1 builds with kmer_table=True (FMX_FLAG_KMER_TABLE, which
-the wide engine honours since round 7; "kmer_k" in the output says what the index got, "count_checksum" must not move).
+the wide engine honours since round 7; "kmer_k" in the output says what the index got, "count_checksum" must not move);
+PAIR=1 builds with pair_index=True (FMX_FLAG_PAIR_INDEX, honoured there since round 8; "pair_index" in the output).
 """
 import ctypes as C
 import json
@@ -27,17 +28,19 @@ def main():
     extra = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     narrow = os.environ.get("NARROW") == "1"
     kmer = os.environ.get("KMER") == "1"
+    pair = os.environ.get("PAIR") == "1"
     n = (1 << log2n) + extra
     dev = torch.device("cuda", 0)
     lib = L.lib()
     text = W.dna_text_torch(n, 17, dev)
     t0 = time.time()
     index = F.FMIndexWithLocate.from_device_text(text.data_ptr(), n, 4, level=2, force_wide=not narrow,
-                                                 kmer_table=kmer)
+                                                 kmer_table=kmer, pair_index=pair)
     build_s = time.time() - t0
     h = index.handle()
     kp, mp = 1 << 20, 32
-    out = {"n": n, "wide": bool(index.is_wide()), "kmer_k": index.kmer_k(), "index_bytes": index.heap_size(),
+    out = {"n": n, "wide": bool(index.is_wide()), "kmer_k": index.kmer_k(), "pair_index": bool(index.has_pair_index()),
+           "index_bytes": index.heap_size(),
            "build_s": round(build_s, 2),
            "env": {k: v for k, v in os.environ.items() if k.startswith("FMXW_")}}
     for label, seed in (("count", 3), ("locate", 5)):

@@ -262,7 +262,9 @@ int fmx_device(const fmx_index *idx) { return idx ? idx->device : -1; }
 uint64_t fmx_num_samples(const fmx_index *idx) { return idx ? idx->nsamples : 0; }
 uint64_t fmx_num_runs(const fmx_index *idx) { return idx ? idx->runs : 0; }
 uint32_t fmx_sym_bytes(const fmx_index *idx) { return idx ? idx->sym_bytes : 0; }
-int fmx_has_pair_index(const fmx_index *idx) { return idx && idx->dev.pair_rec ? 1 : 0; }
+int fmx_has_pair_index(const fmx_index *idx) {
+  return idx && (idx->is_wide ? idx->wpair.rec != nullptr : idx->dev.pair_rec != nullptr) ? 1 : 0;
+}
 int fmx_is_wide(const fmx_index *idx) { return idx && idx->is_wide ? 1 : 0; }
 int fmx_text_order(const fmx_index *idx) {
   return idx && (idx->is_wide ? (idx->wide.walk != nullptr || idx->wide.phase != nullptr) : idx->dev.phase != nullptr) ? 1 : 0;
@@ -1424,11 +1426,13 @@ const char *validate_loaded(const FileHeader &h, const FmxDev &d) {
   return nullptr;
 }
 const size_t kChunk = 64u << 20;
+const uint32_t kFileVersionPair = 12;   // a wide index WITH a pair index: version 11 plus the FmxWidePair section (save_wide); every other index writes 11
 const uint32_t kFileVersion = 11;   // 11: k-mer start table of wide indexes (FmxWideDev::kmer / kmer_k / kmer_bits); 10: wide RLFM indexes (FmxWideDev::b / bp / lfrun); 9: FmxDev::walk (walk records: a presence flag only, rebuilt by fmx_load); 2: select hints every 64 ones (was 512); 3: positions of sparse vectors; 4: wavelet select hints; 5: dense select blocks; 6: pointer fields written as presence flags, fields validated on load; 7: select blocks of 8 / 16 / 32 / 64 ones by density; 8: text-order sampling (phase pieces)
 }  // namespace
 
 // wide indexes (n >= 2^32 - 16): header (dev_struct_bytes carries kWideMark) | FmxWideDev with presence flags for
-// pointers | cs[] | records | bases | samples
+// pointers | cs[] | records | bases | samples ...; an index with a pair index (version kFileVersionPair) has its
+// FmxWidePair (presence flags for pointers) after the FmxWideDev and its pair records | pair bases after every other array
 namespace {
 const uint32_t kWideMark = 0x80000000u;
 struct WideBlobs { const void **field[20 + 2 * FMXW_MAX_LEVELS]; uint64_t bytes[20 + 2 * FMXW_MAX_LEVELS]; int n; };
@@ -1475,6 +1479,16 @@ WideBlobs wide_blobs(FmxWideDev &w, uint64_t nsamples) {
   }
   return b;
 }
+// the pair index of a wide index (FmxWidePair): a section of its own, written only by indexes that have one
+WideBlobs pair_blobs(FmxWidePair &pr, uint64_t n, uint32_t nsb) {
+  WideBlobs b;
+  b.n = 0;
+  if (pr.rec) {
+    b.field[b.n] = (const void **)&pr.rec;  b.bytes[b.n++] = (n / 128u + 1u) * 128ull;
+    b.field[b.n] = (const void **)&pr.base; b.bytes[b.n++] = (uint64_t)nsb * 128ull;
+  }
+  return b;
+}
 }  // namespace
 static int save_wide(const fmx_index *idx, FILE *f, FileHeader &h) {
   h.dev_struct_bytes = (uint32_t)sizeof(FmxWideDev) | kWideMark;
@@ -1483,7 +1497,17 @@ static int save_wide(const fmx_index *idx, FILE *f, FileHeader &h) {
   for (int b = 0; b < bf.n; b++) *bf.field[b] = (const void *)(uintptr_t)1;
   if (wfile.sa_level == FMX_NO_LOCATE) wfile.samples = nullptr;
   wfile.status = nullptr;
+  FmxWidePair psrc = idx->wpair, pfile = idx->wpair;
+  const bool pair = psrc.rec != nullptr;
+  if (pair) {                                       // its own section: the arrays go behind all the others
+    h.version = kFileVersionPair;
+    const WideBlobs ps = pair_blobs(psrc, src.n, src.nsb);
+    for (int b = 0; b < ps.n; b++) { bs.field[bs.n] = ps.field[b]; bs.bytes[bs.n++] = ps.bytes[b]; }
+    pfile.rec = (const uint4 *)(uintptr_t)1;
+    pfile.base = (const uint64_t *)(uintptr_t)1;
+  }
   bool ok = fwrite(&h, sizeof h, 1, f) == 1 && fwrite(&wfile, sizeof wfile, 1, f) == 1 &&
+            (!pair || fwrite(&pfile, sizeof pfile, 1, f) == 1) &&
             fwrite(idx->h_cs, 8, idx->max_character + 1, f) == idx->max_character + 1;
   std::string buf(kChunk, '\0');
   for (int b = 0; ok && b < bs.n; b++) {
@@ -1551,6 +1575,9 @@ int fmx_save(const fmx_index *idx, const char *path) {
 static int load_wide(FILE *f, const FileHeader &h, int device, fmx_index *idx) {
   FmxWideDev w;
   if (fread(&w, sizeof w, 1, f) != 1) return fail(FMX_ERR_ARG, "truncated index file");
+  FmxWidePair pr = {nullptr, nullptr, 0, 0};
+  const bool pair = h.version == kFileVersionPair;   // the file has the pair section
+  if (pair && fread(&pr, sizeof pr, 1, f) != 1) return fail(FMX_ERR_ARG, "truncated index file");
   const bool locate = w.sa_level != FMX_NO_LOCATE;
   const char *bad = nullptr;
   const bool rl = h.kind == FMX_KIND_RLFM, mp = h.kind == FMX_KIND_MULTI;
@@ -1612,6 +1639,15 @@ static int load_wide(FILE *f, const FileHeader &h, int device, fmx_index *idx) {
                     : (w.kmer_k != 0 || w.kmer_bits != 0))
       bad = "k-mer table";
   }
+  if (!bad && pair) {
+    // pair section: both presence flags are exactly 1 (the version says the section is there), the index is one the builder
+    // gives a pair index (one-level FM over u8 symbols, max_character <= 4, n >= 4) and the two rows without a 2-gram are
+    // rows of it -- the record and base blobs must then be in the file
+    if ((uintptr_t)pr.rec != 1 || (uintptr_t)pr.base != 1) bad = "pair index flag";
+    else if (w.generic || h.kind != FMX_KIND_FM || h.sym_bytes != 1 || h.max_character > 4 || h.n < 4 || pr.row0 > h.n ||
+             pr.row1 > h.n)
+      bad = "pair index";
+  }
   if (!bad && rl) {
     const FmxWideBits *v[2] = {&w.b, &w.bp};
     for (int t = 0; t < 2 && !bad; t++) {
@@ -1636,7 +1672,11 @@ static int load_wide(FILE *f, const FileHeader &h, int device, fmx_index *idx) {
   if (fread(idx->h_cs, 8, h.max_character + 1, f) != h.max_character + 1) return fail(FMX_ERR_ARG, "truncated index file");
   const bool has_walk = w.walk != nullptr;          // presence flags of the file, like every blob field
   WideBlobs bs = wide_blobs(w, idx->nsamples);
-  uint64_t need = sizeof(FileHeader) + sizeof(FmxWideDev) + (h.max_character + 1) * 8;
+  if (pair) {
+    const WideBlobs ps = pair_blobs(pr, w.n, w.nsb);
+    for (int b = 0; b < ps.n; b++) { bs.field[bs.n] = ps.field[b]; bs.bytes[bs.n++] = ps.bytes[b]; }
+  }
+  uint64_t need = sizeof(FileHeader) + sizeof(FmxWideDev) + (pair ? sizeof(FmxWidePair) : 0) + (h.max_character + 1) * 8;
   for (int b = 0; b < bs.n; b++) { *bs.field[b] = nullptr; need += bs.bytes[b]; }
   w.samples = nullptr; w.status = nullptr;
   if (!has_walk) { w.walk = nullptr; w.wbase = nullptr; w.nwsb = 0; w.wsb_shift = 0; }
@@ -1663,6 +1703,7 @@ static int load_wide(FILE *f, const FileHeader &h, int device, fmx_index *idx) {
   }
   w.status = idx->dev.status;
   idx->wide = w;
+  idx->wpair = pr;
   idx->is_wide = 1;
   idx->dev.sa_level = w.sa_level;
   idx->dev.kind = h.kind;
@@ -1683,7 +1724,8 @@ int fmx_load(const char *path, int device, fmx_index **out) {
   idx->layout = FMX_LAYOUT;
   int rc = FMX_OK;
   do {
-    if (fread(&h, sizeof h, 1, f) != 1 || memcmp(h.magic, "FMXIDX01", 8) != 0 || h.version != kFileVersion) {
+    if (fread(&h, sizeof h, 1, f) != 1 || memcmp(h.magic, "FMXIDX01", 8) != 0 ||
+        (h.version != kFileVersion && h.version != kFileVersionPair)) {
       rc = fail(FMX_ERR_ARG, "not an fmx index file (or another version)");
       break;
     }
@@ -1691,7 +1733,10 @@ int fmx_load(const char *path, int device, fmx_index **out) {
       rc = load_wide(f, h, device, idx);
       break;
     }
-    if (h.dev_struct_bytes != sizeof(FmxDev)) { rc = fail(FMX_ERR_ARG, "not an fmx index file (or another version)"); break; }
+    if (h.dev_struct_bytes != sizeof(FmxDev) || h.version != kFileVersion) {   // (only wide files have the pair section)
+      rc = fail(FMX_ERR_ARG, "not an fmx index file (or another version)");
+      break;
+    }
     if (fread(&idx->dev, sizeof(FmxDev), 1, f) != 1) { rc = fail(FMX_ERR_ARG, "truncated index file"); break; }
     if (const char *what = validate_loaded(h, idx->dev)) {
       char msg[128];
@@ -1825,6 +1870,7 @@ int fmx_replicate(const fmx_index *src, int device, fmx_index **out) {
       WideBlobs bc = wide_blobs(idx->wide, idx->nsamples);
       for (int b = 0; b < bc.n; b++) *bc.field[b] = nullptr;
       idx->wide.status = nullptr;
+      idx->wpair.rec = nullptr; idx->wpair.base = nullptr;
     } else {
       Blob bc[64];
       const int nc = enumerate_blobs(idx->dev, idx->nsamples, bc);
@@ -1845,6 +1891,12 @@ int fmx_replicate(const fmx_index *src, int device, fmx_index **out) {
         rc = replicate_array(idx, field, *bs.field[b], src->device, bs.bytes[b]);
       }
       idx->wide.status = idx->dev.status;
+      if (rc == FMX_OK && src->wpair.rec) {         // the pair index: records, then bases
+        FmxWidePair sp = src->wpair;
+        const WideBlobs ps = pair_blobs(sp, src->wide.n, src->wide.nsb);
+        rc = replicate_array(idx, (const void **)&idx->wpair.rec, src->wpair.rec, src->device, ps.bytes[0]);
+        if (rc == FMX_OK) rc = replicate_array(idx, (const void **)&idx->wpair.base, src->wpair.base, src->device, ps.bytes[1]);
+      }
     } else {
       FmxDev sd = src->dev, probe = src->dev;
       Blob bs[64], bp[64];

@@ -2272,6 +2272,29 @@ __global__ void kw_bases_g(const uint64_t *__restrict__ scan, uint32_t nrec, uin
   const uint32_t sb = t >> 4, c = t & 15u;
   base[t] = c < ncode ? scan[(size_t)c * nrec + ((size_t)sb << sb_recs)] - (fold ? 0ull : scan[(size_t)c * nrec]) : 0ull;
 }
+// 2-gram BWT of a wide index (FMX_FLAG_PAIR_INDEX; the 64-bit twin of k_bwt2): code = (T[p-2]-1)*4 + (T[p-1]-1),
+// p = SA[i] >= 2; the two rows with p < 2 are stored as code 0 and reported in special[p]
+__global__ __launch_bounds__(BLK) void kw_bwt2(const uint8_t *__restrict__ t, const uint64_t *__restrict__ sa, uint64_t n,
+                                                uint8_t *__restrict__ out, uint64_t *__restrict__ special) {
+  KW_FOR(i, n) {
+    const uint64_t p = sa[i];
+    if (p >= 2) {
+      out[i] = (uint8_t)((t[p - 2] - 1u) * 4u + (t[p - 1] - 1u));
+    } else {
+      out[i] = 0;
+      special[p] = i;
+    }
+  }
+}
+// bases of the pair records: scan laid out [code][record] over 16 codes (as kw_bases_g without the fold), plus
+// k2[code] = lf_map2(c1, cs[c2]) -- so that base + relative counter + popcount IS lf_map2(c1, lf_map2(c2, i))
+__global__ void kw_bases_pair(const uint64_t *__restrict__ scan, uint32_t nrec, uint32_t nsb, uint32_t sb_recs,
+                              const uint64_t *__restrict__ k2, uint64_t *__restrict__ base) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nsb * 16u) return;
+  const uint32_t sb = t >> 4, c = t & 15u;
+  base[t] = k2[c] + scan[(size_t)c * nrec + ((size_t)sb << sb_recs)] - scan[(size_t)c * nrec];
+}
 template <typename T>
 __global__ __launch_bounds__(BLK) void kw_verify_sa(const T *__restrict__ t, const uint64_t *__restrict__ sa,
                                                      uint64_t n, uint32_t *__restrict__ mark, unsigned long long *bad) {
@@ -3048,7 +3071,9 @@ static int build_wide_t(fmx_index *idx, const T *d_text) {
   const uint32_t L = 32u - (uint32_t)__builtin_clz(maxc);   // text.rs:61-63
   // -- every allocation whose size is known from (n, level, alphabet) BEFORE the first kernel touches memory (round 5;
   // DevPool::use_slab says why): the temporaries' slab -- 32 bytes per symbol for the suffix sort's four 8-byte arrays,
-  // which everything later fits into once they are given back -- and, for the one-level index, its own arrays
+  // which everything later fits into once they are given back -- and, for the one-level index, its own arrays.
+  // (Two exceptions, both opt-in: the pair index's arrays wait for the text statistics, which decide whether the text
+  // qualifies -- allocated right after them, when only the histogram kernel has run -- and the k-mer table comes last.)
   uint64_t *pre_samp = nullptr, *pre_wbase = nullptr, *pre_base = nullptr;
   uint4 *pre_walk = nullptr, *pre_rec = nullptr;
   bool pre_walk_records = false;
@@ -3109,6 +3134,23 @@ static int build_wide_t(fmx_index *idx, const T *d_text) {
     for (uint32_t c = 0; c <= maxc; c++) { idx->h_cs[c] = sum; sum += hist[c]; }
   }
   mark("stats");
+  // -- opt-in pair index (FMX_FLAG_PAIR_INDEX; fmx_index::wpair): the 32-bit builder's rule -- sigma <= 4, the
+  // terminator is the only zero, which only the statistics above can tell.  So its arrays are allocated here: after the
+  // histogram kernel has touched a few KiB of the slab, before the suffix sort touches the rest (use_slab) --
+  const bool pair_index = (idx->flags & FMX_FLAG_PAIR_INDEX) && idx->kind == FMX_KIND_FM && sizeof(T) == 1 && maxc <= 4 &&
+                          n >= 4 && hist[0] == 1;
+  // (the superblocks of the FM branches below -- one-level records, generic levels and the pair records share them)
+  const uint32_t sb_shift = fmx_wide_n(n) ? FMX_WIDE_SB_SHIFT : FMX_WIDE_SB_SHIFT_TEST, sb_recs = sb_shift - 8u;
+  const uint32_t nsb = (uint32_t)(n >> sb_shift) + 1u;
+  const uint32_t pair_nrec = (uint32_t)(n / 128u + 1u);
+  uint4 *d_pairrec = nullptr;
+  uint64_t *d_pairbase = nullptr;
+  if (pair_index) {
+    FMX_HIP(fmx_dev_malloc((void **)&d_pairrec, (size_t)pair_nrec * 128));
+    if (int rc = keep(idx, d_pairrec, (uint64_t)pair_nrec * 128)) return rc;
+    FMX_HIP(fmx_dev_malloc((void **)&d_pairbase, (size_t)nsb * 16 * sizeof(uint64_t)));
+    if (int rc = keep(idx, d_pairbase, (uint64_t)nsb * 128)) return rc;
+  }
   // -- suffix array --
   uint64_t *d_sa;
   FMX_HIP(pool.get(&d_sa, n));
@@ -3218,6 +3260,18 @@ static int build_wide_t(fmx_index *idx, const T *d_text) {
   FMX_HIP(pool.get(&d_bwt, n));
   hipLaunchKernelGGL(kw_bwt<T>, dim3(wblocks(n)), dim3(BLK), 0, 0, d_text, d_sa, n, d_bwt);
   FMX_HIP(hipGetLastError());
+  // the 2-gram BWT of the pair index, while text and suffix array are resident
+  uint8_t *d_b2 = nullptr;
+  uint64_t pair_rows[2] = {0, 0};
+  if (pair_index) {
+    uint64_t *d_sp;
+    FMX_HIP(pool.get(&d_b2, n));
+    FMX_HIP(pool.get(&d_sp, 2));
+    hipLaunchKernelGGL(kw_bwt2, dim3(wblocks(n)), dim3(BLK), 0, 0, (const uint8_t *)d_text, d_sa, n, d_b2, d_sp);
+    FMX_HIP(hipGetLastError());
+    FMX_HIP(hipMemcpy(pair_rows, d_sp, sizeof pair_rows, hipMemcpyDeviceToHost));
+    pool.release(d_sp);
+  }
   if (walk_records) {
     if constexpr (sizeof(T) == 1) {
       const uint32_t level = w.sa_level;
@@ -3337,8 +3391,6 @@ static int build_wide_t(fmx_index *idx, const T *d_text) {
     idx->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return FMX_OK;
   }
-  const uint32_t sb_shift = fmx_wide_n(n) ? FMX_WIDE_SB_SHIFT : FMX_WIDE_SB_SHIFT_TEST, sb_recs = sb_shift - 8u;
-  const uint32_t nsb = (uint32_t)(n >> sb_shift) + 1u;
   if (maxc > 7 || sizeof(T) != 1 || idx->kind == FMX_KIND_MULTI) {
     // -- generic wide index: the levels of the multi-ary wavelet matrix (as build_mwm, 64-bit scans) --
     if (int rc = build_wide_levels<T>(idx, d_bwt, n, L, pool)) return rc;
@@ -3392,6 +3444,43 @@ static int build_wide_t(fmx_index *idx, const T *d_text) {
   w.sb_shift = sb_shift;
   idx->is_wide = 1;
   mark("records");
+  idx->wpair = FmxWidePair{nullptr, nullptr, 0, 0};
+  if (pair_index) {
+    // K2[c1c2] = LF(c1, LF(c2, 0)) = lf_map2(c1, cs[c2])   (fm_index.rs:93-95 applied twice), on the finished records
+    uint64_t hq[32];
+    for (uint32_t code = 0; code < 16; code++) {
+      const uint32_t c1 = code / 4 + 1, c2 = code % 4 + 1;
+      hq[code] = c1 <= maxc ? c1 : 1;
+      hq[16 + code] = c2 <= maxc ? idx->h_cs[c2] : 0;
+    }
+    uint64_t *d_q, *d_pscan;
+    uint32_t *d_phist;
+    FMX_HIP(pool.get(&d_q, 48));
+    FMX_HIP(hipMemcpy(d_q, hq, sizeof hq, hipMemcpyHostToDevice));
+    if (int rc = fmxw_launch_scalar(idx, 2, d_q, d_q + 16, 16, d_q + 32, 0)) return rc;
+    // fmt-4 planes + per-record histograms, 64-bit scan, relative counters + superblock bases (as the records above)
+    FMX_HIP(pool.get(&d_phist, (size_t)pair_nrec * 16));
+    FMX_HIP(pool.get(&d_pscan, (size_t)pair_nrec * 16));
+    hipLaunchKernelGGL((k_mwm_pieces<4, uint8_t>), dim3(nblocks((uint64_t)pair_nrec * 8)), dim3(BLK), 0, 0, d_b2, n, 0u, 15u,
+                       pair_nrec, d_pairrec, d_phist);
+    {
+      size_t tb = 0;
+      FMX_HIP(exclusive_sum(nullptr, tb, d_phist, d_pscan, (size_t)pair_nrec * 16));
+      uint8_t *tmp;
+      FMX_HIP(pool.get(&tmp, tb));
+      FMX_HIP(exclusive_sum(tmp, tb, d_phist, d_pscan, (size_t)pair_nrec * 16));
+      pool.release(tmp);
+    }
+    hipLaunchKernelGGL(kw_counters_g<4>, dim3(nblocks((uint64_t)pair_nrec * 8)), dim3(BLK), 0, 0, d_pscan, pair_nrec,
+                       sb_shift - 7u, d_pairrec);
+    hipLaunchKernelGGL(kw_bases_pair, dim3((nsb * 16 + 63) / 64), dim3(64), 0, 0, d_pscan, pair_nrec, nsb,
+                       sb_shift - 7u, d_q + 32, d_pairbase);
+    FMX_HIP(hipGetLastError());
+    FMX_HIP(hipDeviceSynchronize());
+    pool.release(d_pscan); pool.release(d_phist); pool.release(d_q); pool.release(d_b2);
+    idx->wpair = FmxWidePair{d_pairrec, d_pairbase, pair_rows[0], pair_rows[1]};
+    mark("pair index");
+  }
   if (int rc = build_wide_kmer<T>(idx)) return rc;
   mark("k-mer table");
   idx->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

@@ -234,6 +234,20 @@ struct FmxWideDev {  // passed BY VALUE to the wide kernels
   uint32_t kmer_k;           // symbols per entry (0 = no table)
   uint32_t kmer_bits;        // bits per symbol in the table index (symbol c is coded c - 1)
 };
+// FMX_FLAG_PAIR_INDEX on the wide engine (round 8; one-level FM indexes over u8 symbols, max_character <= 4, n >= 4, the
+// terminator the only zero -- FmxDev::pair_rec is the 32-bit engine's).  A struct of its own, handed to
+// fmxw_count_pair_kernel NEXT TO FmxWideDev and written as its own section of an index file: FmxWideDev, and with it
+// every kernel of an index without the flag, is what it was before the pair index existed.
+//   rec:  n / 128 + 1 fmt-4 records over the 2-gram BWT (row n is addressable), their 16 counters RELATIVE to the
+//         record's superblock -- the 2^sb_shift rows of FmxWideDev::rec, so 2^(sb_shift - 7) records;
+//   base: [nsb][16], the 64-bit values at the superblock's start with K2[c1c2] = lf_map2(c1, cs[c2]) folded in:
+//             lf_map2(c1, lf_map2(c2, i)) = base[i >> sb_shift][c1c2] + cnt32[record(i)][c1c2] + popcount
+//   row0, row1: the two rows without a 2-gram (SA = 0 and SA = 1), stored as code 0 and subtracted from its rank.
+struct FmxWidePair {
+  const uint4 *rec;          // NULL: the index has no pair index
+  const uint64_t *base;
+  uint64_t row0, row1;
+};
 #define FMXW_WALK_SB_SHIFT 24u     // records per walk superblock: 2^24 x 112 rows < 2^31, so relative counters fit 32 bits
 #define FMXW_WALK_SB_SHIFT_TEST 5u  // FMX_FLAG_FORCE_WIDE: 32 records, so that a small text has many superblocks
 
@@ -268,6 +282,7 @@ struct fmx_index {
   hipEvent_t *ev_series; // timing == 2: FMX_SERIES_CAP pairs, created on first use
   int series_n;
   uint64_t *d_steps;     // device counter
+  FmxWidePair wpair;     // wide + FMX_FLAG_PAIR_INDEX (last member: nothing above it moves)
 };
 
 // The measurement libraries (libfmx_census.so, libfmx_measure.so, libfmx_debug.so) take handles made by libfmx.so: same

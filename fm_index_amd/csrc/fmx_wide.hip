@@ -18,6 +18,8 @@
 // FMX_FLAG_KMER_TABLE (round 7): the KM = true instantiations of fmxw_count_kernel / fmxw_g_count_ep_kernel take a fresh
 // pattern's first kmer_k steps from one 16-byte entry of FmxWideDev::kmer (built by fmxw_kmer_build_kernel /
 // fmxw_g_kmer_build_kernel); KM = false is the code of the indexes without a table, unchanged.
+// FMX_FLAG_PAIR_INDEX (round 8): one-level indexes with fmx_index::wpair (FmxWidePair) count through fmxw_count_pair_kernel -- two
+// pattern symbols per probe of the 2-gram records; every other index runs the kernels it ran before.
 #include "fmx_device.h"
 
 #define FMXW_BLOCK 256
@@ -196,6 +198,131 @@ __global__ __launch_bounds__(FMXW_BLOCK) void fmxw_count_kernel(
       c = cn;
       j--;
       nsteps++;
+      if (s == e) break;                            // wrapper.rs:111-113
+    }
+    if (g == 0) {
+      if (out_s) out_s[k] = s;
+      if (out_e) out_e[k] = e;
+      if (out_cnt) out_cnt[k] = e - s;              // wrapper.rs:132-134
+    }
+  }
+  if (steps_out && g == 0 && nsteps) atomicAdd((unsigned long long *)steps_out, (unsigned long long)nsteps);
+}
+
+// The bases of the pair records (FmxWidePair::base, 16 per superblock) next to FMXW_BASES: LDS up to FMXW_LDS_SB
+// superblocks (64 x (8 + 16) x 8 bytes = 12 KiB per block with both tables), else global memory.
+#define FMXW_PAIR_BASES(w, pr, LDSB)                                                                             \
+  __shared__ uint64_t lds_pbase[(LDSB) ? FMXW_LDS_SB * 16u : 1u];                                                \
+  if (LDSB) {                                                                                                  \
+    for (uint32_t t_ = threadIdx.x; t_ < (w).nsb * 16u; t_ += blockDim.x) lds_pbase[t_] = (pr).base[t_];        \
+    __syncthreads();                                                                                           \
+  }                                                                                                            \
+  auto pbase_at = [&](uint64_t row_, uint32_t code_) -> uint64_t {                                             \
+    const uint32_t sb_ = (uint32_t)(row_ >> (w).sb_shift);                                                     \
+    if constexpr (LDSB) return lds_pbase[sb_ * 16u + code_]; else return (pr).base[(size_t)sb_ * 16u + code_];     \
+  }
+
+// count with the opt-in pair index (FMX_FLAG_PAIR_INDEX; the wide twin of fmx_count_pair_kernel): while at least two
+// symbols remain, both in 1..max_character (<= 4), ONE probe of the 2-gram records per interval end advances TWO symbols:
+//     LF(c1, LF(c2, i)) = pr.base[sb(i)][c1c2] + cnt32[c1c2] + popcount         (K2 folded into the bases)
+// otherwise the one-step path of fmxw_count_kernel.  The reference's early exit (wrapper.rs:111-113) as on the 32-bit
+// engine: when the pair step collapses the interval, the single step for the LAST symbol decides whether the reference
+// would have stopped after one symbol (then ITS (s, e) is returned) or after two.  The for-loop shape of
+// fmxw_count_kernel, one pattern per group at a time; the next TWO pattern symbols ride along with the record loads.
+// KM: as fmxw_count_kernel -- a fresh pattern's first kmer_k steps from one table entry.
+template <bool LDSB, bool KM>
+__global__ __launch_bounds__(FMXW_BLOCK) void fmxw_count_pair_kernel(
+    FmxWideDev w, FmxWidePair pr, const uint8_t *__restrict__ pat, const uint64_t *__restrict__ off, uint64_t npat,
+    const uint64_t *__restrict__ s0e0, uint64_t *__restrict__ out_s, uint64_t *__restrict__ out_e,
+    uint64_t *__restrict__ out_cnt, uint64_t *__restrict__ steps_out) {
+  FMXW_BASES(w, LDSB);
+  FMXW_PAIR_BASES(w, pr, LDSB);
+  const uint32_t g = threadIdx.x & (FMX_GROUP - 1);
+  const uint64_t gid = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / FMX_GROUP;
+  const uint64_t ngroups = ((uint64_t)gridDim.x * blockDim.x) / FMX_GROUP;
+  const uint64_t ptot = npat ? off[npat] : 0;       // symbols the caller declares behind `pat`
+  const uint64_t pmin = npat ? off[0] : 0;      // ... starting at this symbol (a slice of a larger batch keeps its absolute offsets)
+  uint64_t nsteps = 0;
+  for (uint64_t k = gid; k < npat; k += ngroups) {
+    const uint64_t pbeg = off[k], pend = off[k + 1];
+    uint64_t j = pend - pbeg;
+    // offsets that go backwards or leave the pattern buffer: refuse, do not read
+    bool bad = pend < pbeg || pbeg < pmin || pend > ptot;
+    uint64_t s = 0, e = w.n;                        // SearchIndexWrapper::search: (0, len)   wrapper.rs:41
+    if (s0e0) {                                     // Search::search on an existing Search   wrapper.rs:105-106
+      s = s0e0[2 * k];
+      e = s0e0[2 * k + 1];
+      bad |= s > w.n || e > w.n;                    // not a range of this index
+    }
+    if (bad) {
+      if (g == 0) atomicOr(w.status, 1u << FMX_ERR_ARG);
+      s = 0; e = 0; j = 0;
+    }
+    if constexpr (KM) {
+      if (!s0e0 && j >= w.kmer_k) {                 // the first kmer_k steps from the table (a refused pattern has j = 0)
+        uint32_t code;
+        if (fmx_kmer_code(pat, pbeg + j, w.kmer_k, w.kmer_bits, w.max_character, g, code)) {
+          FMX_CHECK(code < (1u << (w.kmer_bits * w.kmer_k)));
+          FMX_TOUCH_G0N(g, &w.kmer[code]);
+          const FmxWideKmer se = w.kmer[code];
+          s = se.s;
+          e = se.e;
+          j = se.s == se.e ? 0u : j - w.kmer_k;     // empty already: the reference's break   wrapper.rs:111-113
+          nsteps += w.kmer_k;
+        }                                           // a 0 or a symbol > max_character among them: the stepwise path decides
+      }
+    }
+    uint32_t c2 = j ? pat[pbeg + j - 1] : 0u;       // c2 = last unread symbol, c1 = the one before it   wrapper.rs:108
+    uint32_t c1 = j > 1 ? pat[pbeg + j - 2] : 0u;
+    while (j) {
+      if (c2 > w.max_character) {                   // reference: panic on cs[c]
+        if (g == 0) atomicOr(w.status, 1u << FMX_ERR_SYMBOL_RANGE);
+        s = 0; e = 0;
+        break;
+      }
+      // (a c1 above max_character is left to the one-step path: it is refused when the reference reaches it)
+      const bool pair = j >= 2 && (c2 - 1u) < w.max_character && (c1 - 1u) < w.max_character;
+      FMX_CHECK((s >> w.sb_shift) < w.nsb && (e >> w.sb_shift) < w.nsb);
+      // the two symbols after these ride along with the record loads
+      const uint32_t n1 = j > 2 ? pat[pbeg + j - 3] : 0u;
+      const uint32_t n2 = j > 3 ? pat[pbeg + j - 4] : 0u;
+      uint32_t used = 1;
+      if (pair) {
+        const uint32_t code = (c1 - 1u) * 4u + (c2 - 1u);
+        FMX_CHECK((s >> 7) < w.n / 128u + 1u && (e >> 7) < w.n / 128u + 1u);
+        FMX_TOUCH_G0(g, &pr.rec[(size_t)(s >> 7) * 8u]);
+        if ((e >> 7) != (s >> 7)) FMX_TOUCH_G0(g, &pr.rec[(size_t)(e >> 7) * 8u]);
+        const uint4 pa = pr.rec[(size_t)(s >> 7) * 8u + g], pb = pr.rec[(size_t)(e >> 7) * 8u + g];
+        const uint64_t ba = pbase_at(s, code), bb = pbase_at(e, code);
+        uint64_t ns = ba + fmx_group_sum(fmx_piece_rank<4>(pa, (uint32_t)s & 127u, code, g));
+        uint64_t ne = bb + fmx_group_sum(fmx_piece_rank<4>(pb, (uint32_t)e & 127u, code, g));
+        if (code == 0u) {                           // the two rows without a 2-gram are stored as code 0
+          ns -= (uint64_t)(s > pr.row0) + (uint64_t)(s > pr.row1);
+          ne -= (uint64_t)(e > pr.row0) + (uint64_t)(e > pr.row1);
+        }
+        used = 2;
+        if (ns == ne) {                             // would the reference already have stopped after the last symbol alone?
+          FMX_CHECK((e >> 8) < w.n / 256u + 1u && (s >> 8) < w.n / 256u + 1u);
+          FMX_TOUCH_G0(g, &w.rec[(size_t)(s >> 8) * 8u]);
+          if ((e >> 8) != (s >> 8)) FMX_TOUCH_G0(g, &w.rec[(size_t)(e >> 8) * 8u]);
+          const uint4 qa =w.rec[(size_t)(s >> 8) * 8u + g], qb = w.rec[(size_t)(e >> 8) * 8u + g];
+          const uint64_t s1 = base_at(s, c2) + fmx_group_sum(fmx_piece_rank<3>(qa, (uint32_t)s & 255u, c2, g));
+          const uint64_t e1 = base_at(e, c2) + fmx_group_sum(fmx_piece_rank<3>(qb, (uint32_t)e & 255u, c2, g));
+          if (s1 == e1) { ns = s1; ne = e1; used = 1; }
+        }
+        s = ns; e = ne;
+      } else {
+        FMX_CHECK((e >> 8) < w.n / 256u + 1u && (s >> 8) < w.n / 256u + 1u);
+        FMX_TOUCH_G0(g, &w.rec[(size_t)(s >> 8) * 8u]);
+        if ((e >> 8) != (s >> 8)) FMX_TOUCH_G0(g, &w.rec[(size_t)(e >> 8) * 8u]);
+        const uint4 pa = w.rec[(size_t)(s >> 8) * 8u + g], pb = w.rec[(size_t)(e >> 8) * 8u + g];
+        const uint64_t ba = base_at(s, c2), bb = base_at(e, c2);
+        s = ba + fmx_group_sum(fmx_piece_rank<3>(pa, (uint32_t)s & 255u, c2, g));      // wrapper.rs:109
+        e = bb + fmx_group_sum(fmx_piece_rank<3>(pb, (uint32_t)e & 255u, c2, g));      // wrapper.rs:110
+      }
+      nsteps += used;
+      j -= used;
+      if (used == 2) { c2 = n1; c1 = n2; } else { c2 = c1; c1 = n1; }
       if (s == e) break;                            // wrapper.rs:111-113
     }
     if (g == 0) {
@@ -1956,7 +2083,15 @@ int fmxw_launch_count(const fmx_index *idx, const void *d_pat, const uint64_t *d
 #define FMXW_CNT(LDSB, KM)                                                                                         \
   hipLaunchKernelGGL((fmxw_count_kernel<LDSB, KM>), dim3(fmxw_grid(npat)), dim3(FMXW_BLOCK), 0, st, w,               \
                      (const uint8_t *)d_pat, d_off, npat, d_s0e0, d_s, d_e, d_cnt, idx->timing == 1 ? idx->d_steps : nullptr)
-  if (w.kmer) { if (w.nsb <= FMXW_LDS_SB) FMXW_CNT(true, true); else FMXW_CNT(false, true); }
+#define FMXW_PCNT(LDSB, KM)                                                                                        \
+  hipLaunchKernelGGL((fmxw_count_pair_kernel<LDSB, KM>), dim3(fmxw_grid(npat)), dim3(FMXW_BLOCK), 0, st, w,          \
+                     idx->wpair, (const uint8_t *)d_pat, d_off, npat, d_s0e0, d_s, d_e, d_cnt,                      \
+                     idx->timing == 1 ? idx->d_steps : nullptr)
+  if (idx->wpair.rec) {                                 // FMX_FLAG_PAIR_INDEX: two symbols per probe
+    if (w.kmer) { if (w.nsb <= FMXW_LDS_SB) FMXW_PCNT(true, true); else FMXW_PCNT(false, true); }
+    else if (w.nsb <= FMXW_LDS_SB) FMXW_PCNT(true, false); else FMXW_PCNT(false, false);
+  }
+  else if (w.kmer) { if (w.nsb <= FMXW_LDS_SB) FMXW_CNT(true, true); else FMXW_CNT(false, true); }
   else if (w.nsb <= FMXW_LDS_SB) FMXW_CNT(true, false); else FMXW_CNT(false, false);
   fmxw_time_end(idx, st);
   FMX_HIP(hipGetLastError());

@@ -18,8 +18,9 @@
  *    FMX_KIND_FM over u8 with max_character <= 7 -- DNA -- has the faster one-level kernels): every entry point
  *    works on it (build, count, locate, offsets, the trait calls, piece ids and match rows of a multi-pieces index,
  *    extract, save / load, the exports -- the samples through fmx_export_sa_samples64) except fmx_export_sa.  Of the
- *    opt-in accelerators it honours FMX_FLAG_KMER_TABLE (below); FMX_FLAG_PAIR_INDEX is still ignored there, and the
- *    default index of a text that long gets neither (the table is by request only).
+ *    opt-in accelerators it honours FMX_FLAG_KMER_TABLE and FMX_FLAG_PAIR_INDEX (below; the pair index on FMX_KIND_FM
+ *    over u8 symbols with max_character <= 4, n >= 4 and no interior zero, for +1 byte per symbol), and the default
+ *    index of a text that long gets neither (both are by request only on this engine).
  *  - symbols are `sym_bytes` wide: Character = u8 / u16 / u32 / u64 (character.rs:38-42) =
  *    1 / 2 / 4 / 8.  u64 texts are narrowed to u32 at build time (fmx_build on the host, fmx_build_dev by a
  *    kernel), u64 patterns by the host-pointer entry points; the *_dev query entry points take symbols of
@@ -74,7 +75,10 @@ typedef struct fmx_index fmx_index;
  * zeros): a second rank structure over the 2-gram BWT lets one record probe consume TWO pattern
  * symbols (LF(c1, LF(c2, i)) = K2[c1c2] + rank_{c1c2}(BWT2, i)).  Results -- including the
  * (s, e) pair left by the early exit of wrapper.rs:111-113 -- are bit-identical to the 1-step
- * path; +1 byte per text symbol of HBM.  Ignored (1-step index only) when not applicable. */
+ * path; +1 byte per text symbol of HBM.  Ignored (1-step index only) when not applicable.
+ * FMX_KIND_FM over u8 symbols only, n >= 4.  Texts of 2^32 - 16 symbols or more (the 64-bit engine) qualify under the
+ * same rule -- there the records' counters are relative to a 2^31-row superblock, +128 bytes per superblock -- but get
+ * the structure by this flag only, never by default; fmx_has_pair_index() tells what an index got. */
 #define FMX_FLAG_PAIR_INDEX 2u
 /* Opt-in k-mer start table (u8 symbols; RLFM, and FM / multi-pieces with max_character <= 15,
  * i.e. one wavelet level): for every k-mer over the symbols
