@@ -212,6 +212,12 @@ class _Index:
                                          _p(c)))
         return SearchBatch(self, s[:npat], e[:npat], c[:npat])
 
+    def suffix_match_many(self, patterns=None, flat=None, off=None, s0e0=None, min_count=1):
+        """longest suffix of every pattern whose interval keeps >= min_count rows (fmx_suffix_match_batch): a
+        SearchBatch of that interval with `.lengths` (numpy u64), so `.locate()` gives the seed positions.  A symbol
+        above max_character ends a pattern's match and is no error."""
+        return _suffix_match(self, self._lib.fmx_suffix_match_batch, (self._h,), patterns, flat, off, s0e0, min_count)
+
     def locate_many(self, s, e):
         """(offsets u64[npat+1], positions u64[total]) in the reference's iteration order."""
         s = np.ascontiguousarray(s, dtype=np.uint64)
@@ -345,6 +351,19 @@ class _Index:
             pass
 
 
+def _suffix_match(owner, fn, head, patterns, flat, off, s0e0, min_count):
+    """shared by _Index / Replicas .suffix_match_many: `fn(*head, pat, off, npat, s0e0, min_count, s, e, count, len)`"""
+    if flat is None:
+        flat, off = pack_patterns(patterns, owner._dtype)
+    flat = _sym(flat, owner._dtype)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    npat = len(off) - 1
+    s, e, c, ln = (np.zeros(max(npat, 1), dtype=np.uint64) for _ in range(4))
+    se = None if s0e0 is None else np.ascontiguousarray(s0e0, dtype=np.uint64)
+    _check(fn(*head, _p(flat), _p(off), npat, _p(se), int(min_count), _p(s), _p(e), _p(c), _p(ln)))
+    return SearchBatch(owner, s[:npat], e[:npat], c[:npat], ln[:npat])
+
+
 class Replicas:
     """One batch over several replicas of an index from ONE host caller (include/fmx.h: fmx_count_batch_multi /
     fmx_locate_batch_multi; BASELINE config 5).  Patterns are independent (wrapper.rs:103-124), so pattern k of N goes to
@@ -386,6 +405,11 @@ class Replicas:
         _check(self._lib.fmx_count_batch_multi(self._handles(), len(self.indexes), _p(flat), _p(off), npat, _p(se),
                                                _p(s), _p(e), _p(c)))
         return SearchBatch(self, s[:npat], e[:npat], c[:npat])
+
+    def suffix_match_many(self, patterns=None, flat=None, off=None, s0e0=None, min_count=1):
+        """_Index.suffix_match_many over the replicas (fmx_suffix_match_batch_multi)"""
+        return _suffix_match(self, self._lib.fmx_suffix_match_batch_multi, (self._handles(), len(self.indexes)),
+                             patterns, flat, off, s0e0, min_count)
 
     def locate_many(self, s, e):
         s = np.ascontiguousarray(s, dtype=np.uint64)
@@ -555,13 +579,15 @@ class Match:
 
 
 class SearchBatch:
-    """Result of search_many: per-pattern (s, e, count) arrays (numpy u64)."""
+    """Result of search_many: per-pattern (s, e, count) arrays (numpy u64); of suffix_match_many: the same for the
+    longest matching suffix, plus `lengths` (symbols matched; None after search_many)."""
 
-    def __init__(self, index, s, e, counts):
+    def __init__(self, index, s, e, counts, lengths=None):
         self._ix = index
         self.s = s
         self.e = e
         self.counts = counts
+        self.lengths = lengths
 
     def count(self):
         return self.counts

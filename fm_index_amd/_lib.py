@@ -73,6 +73,8 @@ SYMBOLS = [
     ("fmx_count_batch_dev", _I, [_V, _V, _V, _U64, _V, _V, _V, _V, _V]),
     ("fmx_count_batch", _I, [_V, _V, _V, _U64, _V, _V, _V, _V]),
     ("fmx_stream_status", _I, [_V]),
+    ("fmx_suffix_match_batch_dev", _I, [_V, _V, _V, _U64, _V, _U64, _V, _V, _V, _V, _V]),
+    ("fmx_suffix_match_batch", _I, [_V, _V, _V, _U64, _V, _U64, _V, _V, _V, _V]),
     ("fmx_locate_batch_dev", _I, [_V, _V, _V, _U64, _V, _U64, _V, _V]),
     ("fmx_locate_batch", _I, [_V, _V, _V, _U64, _V, _V]),
     ("fmx_offsets_dev", _I, [_V, _V, _V, _U64, _V, _V]),
@@ -83,6 +85,7 @@ SYMBOLS = [
     ("fmx_replicate", _I, [_V, _I, C.POINTER(_V)]),
     ("fmx_shard_range", None, [_U64, _U32, _U32, C.POINTER(_U64), C.POINTER(_U64)]),
     ("fmx_count_batch_multi", _I, [_V, _U32, _V, _V, _U64, _V, _V, _V, _V]),
+    ("fmx_suffix_match_batch_multi", _I, [_V, _U32, _V, _V, _U64, _V, _U64, _V, _V, _V, _V]),
     ("fmx_count_batch_multi_resident", _I, [_V, _U32, _V, _V, _U64, _V, _V, _V, _V]),
     ("fmx_locate_batch_multi", _I, [_V, _U32, _V, _V, _U64, _V, _V]),
     ("fmx_set_timing", None, [_V, _I]),

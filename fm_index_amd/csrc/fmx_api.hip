@@ -377,6 +377,14 @@ int fmx_count_batch_dev(const fmx_index *idx, const void *d_pat, const uint64_t 
   return fmx_launch_count(idx, d_pat, d_pat_off, npat, d_s0e0, d_out_s, d_out_e,
                           d_out_count, (hipStream_t)stream);
 }
+int fmx_suffix_match_batch_dev(const fmx_index *idx, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat,
+                               const uint64_t *d_s0e0, uint64_t min_count, uint64_t *d_out_s, uint64_t *d_out_e,
+                               uint64_t *d_out_count, uint64_t *d_out_len, void *stream) {
+  CHECK_IDX(idx);
+  if (npat && (!d_pat_off)) return fail(FMX_ERR_ARG, "pat_off is NULL");
+  return fmx_launch_suffix_match(idx, d_pat, d_pat_off, npat, d_s0e0, min_count, d_out_s, d_out_e, d_out_count,
+                                 d_out_len, (hipStream_t)stream);
+}
 int fmx_offsets_dev(const fmx_index *idx, const uint64_t *d_s, const uint64_t *d_e, uint64_t npat,
                     uint64_t *d_out_off, void *stream) {
   CHECK_IDX(idx);
@@ -1048,6 +1056,56 @@ int fmx_count_resident_slice(const fmx_index *idx, const void *d_pat, const uint
   if (out_s) FMX_HIP(hipMemcpyAsync(out_s, d_s, b_out, hipMemcpyDeviceToHost, S));
   if (out_e) FMX_HIP(hipMemcpyAsync(out_e, d_e, b_out, hipMemcpyDeviceToHost, S));
   if (out_count) FMX_HIP(hipMemcpyAsync(out_count, d_c, b_out, hipMemcpyDeviceToHost, S));
+  return finish_host_call(sx);
+}
+// Host arrays in, host arrays out: upload, one launch, download, on the calling thread's stream (none of the chunk
+// pipelines of fmx_count_batch).  Like fmx_count_batch the call moves pat[pat_off[0] .. pat_off[npat]) only and the
+// kernels keep the caller's absolute offsets (fmx_suffix_match_batch_multi's shards).
+int fmx_suffix_match_batch(const fmx_index *idx, const void *pat, const uint64_t *pat_off, uint64_t npat,
+                           const uint64_t *s0e0, uint64_t min_count, uint64_t *out_s, uint64_t *out_e,
+                           uint64_t *out_count, uint64_t *out_len) {
+  CHECK_IDX(idx);
+  if (npat == 0) return FMX_OK;
+  if (!pat_off) return fail(FMX_ERR_ARG, "pat_off is NULL");
+  const uint64_t total = pat_off[npat], first = pat_off[0];
+  if (first > total) return fail(FMX_ERR_ARG, "pat_off is not non-decreasing");
+  const uint64_t span = total - first;
+  if (span && !pat) return fail(FMX_ERR_ARG, "pat is NULL");
+  const uint32_t sb = idx->sym_bytes;  // device symbol width
+  std::vector<uint32_t> narrow;
+  const uint8_t *src = (const uint8_t *)pat + first * sb;        // the first symbol this call reads
+  if (idx->sym_bytes_abi == 8 && span) {  // u64 patterns: narrow, saturating so out-of-range stays out of range
+    narrow.resize((size_t)span);
+    const uint64_t *p64 = (const uint64_t *)pat + first;
+    for (uint64_t i = 0; i < span; i++) narrow[i] = p64[i] > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)p64[i];
+    src = (const uint8_t *)narrow.data();
+  }
+  const size_t b_pat = (size_t)span * sb, b_out = (size_t)npat * 8, b_off = (size_t)(npat + 1) * 8;
+  HostCall hc;
+  FMX_HIP(hc.open(idx->device, HostCall::pad(b_pat + 32) + HostCall::pad(b_off) + (s0e0 ? HostCall::pad(2 * b_out) : 0) +
+                                   4 * HostCall::pad(b_out)));
+  uint8_t *d_pat = hc.take<uint8_t>(b_pat + 32);
+  uint64_t *d_off = hc.take<uint64_t>(b_off);
+  uint64_t *d_se = s0e0 ? hc.take<uint64_t>(2 * b_out) : nullptr;
+  uint64_t *d_s = hc.take<uint64_t>(b_out), *d_e = hc.take<uint64_t>(b_out), *d_c = hc.take<uint64_t>(b_out);
+  uint64_t *d_l = hc.take<uint64_t>(b_out);
+  SmallCtx *sx = hc.sx;
+  hipStream_t S = sx->st;
+  CallStatus cs(sx);
+  FMX_HIP(hipMemsetAsync(status_dev(sx), 0, 4, S));
+  if (b_pat) FMX_HIP(hipMemcpyAsync(d_pat, src, b_pat, hipMemcpyHostToDevice, S));
+  FMX_HIP(hipMemcpyAsync(d_off, pat_off, b_off, hipMemcpyHostToDevice, S));
+  if (s0e0) FMX_HIP(hipMemcpyAsync(d_se, s0e0, 2 * b_out, hipMemcpyHostToDevice, S));
+  // (virtual: symbol 0 of the caller's buffer -- never dereferenced below symbol `first`)
+  if (int rc = fmx_launch_suffix_match(idx, d_pat - first * sb, d_off, npat, d_se, min_count, out_s ? d_s : nullptr,
+                                       out_e ? d_e : nullptr, out_count ? d_c : nullptr, out_len ? d_l : nullptr, S)) {
+    (void)hipStreamSynchronize(S);
+    return rc;
+  }
+  if (out_s) FMX_HIP(hipMemcpyAsync(out_s, d_s, b_out, hipMemcpyDeviceToHost, S));
+  if (out_e) FMX_HIP(hipMemcpyAsync(out_e, d_e, b_out, hipMemcpyDeviceToHost, S));
+  if (out_count) FMX_HIP(hipMemcpyAsync(out_count, d_c, b_out, hipMemcpyDeviceToHost, S));
+  if (out_len) FMX_HIP(hipMemcpyAsync(out_len, d_l, b_out, hipMemcpyDeviceToHost, S));
   return finish_host_call(sx);
 }
 void fmx_set_error_text(const char *text) { g_last_error = text ? text : ""; }

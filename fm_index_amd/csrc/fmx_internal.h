@@ -334,6 +334,9 @@ static inline bool fmx_wide_build(const fmx_index *idx) { return fmx_wide_n(idx-
 int fmx_build_wide(fmx_index *idx, const void *d_text);
 int fmxw_launch_count(const fmx_index *idx, const void *d_pat, const uint64_t *d_off, uint64_t npat,
                       const uint64_t *d_s0e0, uint64_t *d_s, uint64_t *d_e, uint64_t *d_cnt, hipStream_t st);
+int fmxw_launch_suffix_match(const fmx_index *idx, const void *d_pat, const uint64_t *d_off, uint64_t npat,
+                             const uint64_t *d_s0e0, uint64_t min_count, uint64_t *d_s, uint64_t *d_e, uint64_t *d_cnt,
+                             uint64_t *d_len, hipStream_t st);
 int fmxw_launch_locate(const fmx_index *idx, const uint64_t *d_s, const uint64_t *d_e, uint64_t npat,
                        const uint64_t *d_off, uint64_t total, uint64_t *d_pos, hipStream_t st);
 int fmxw_launch_scalar(const fmx_index *idx, int op, const uint64_t *d_c, const uint64_t *d_i, uint64_t k,
@@ -382,6 +385,11 @@ static inline int fmx_keep(fmx_index *idx, void *p, uint64_t bytes) {
 int fmx_launch_count(const fmx_index *idx, const void *d_pat, const uint64_t *d_off,
                      uint64_t npat, const uint64_t *d_s0e0, uint64_t *d_s, uint64_t *d_e,
                      uint64_t *d_cnt, hipStream_t st, unsigned max_blocks = 0);
+// longest suffix of every pattern whose interval keeps >= min_count rows (0 = 1): that interval and its length
+// (fmx_suffix.h / fmx_wide_suffix.h; any output may be NULL)
+int fmx_launch_suffix_match(const fmx_index *idx, const void *d_pat, const uint64_t *d_off, uint64_t npat,
+                            const uint64_t *d_s0e0, uint64_t min_count, uint64_t *d_s, uint64_t *d_e,
+                            uint64_t *d_cnt, uint64_t *d_len, hipStream_t st);
 // rows_ws / tile_ws: caller-provided scratch (fmx_locate_rows_bytes / fmx_offsets_tile_bytes); NULL = take
 // it from the stream-ordered allocator for the duration of the call
 int fmx_launch_locate(const fmx_index *idx, const uint64_t *d_s, const uint64_t *d_e,

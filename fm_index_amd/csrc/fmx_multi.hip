@@ -152,6 +152,23 @@ int fmx_count_batch_multi(fmx_index *const *idx, uint32_t ndev, const void *pat,
   });
 }
 
+int fmx_suffix_match_batch_multi(fmx_index *const *idx, uint32_t ndev, const void *pat, const uint64_t *pat_off,
+                                 uint64_t npat, const uint64_t *s0e0, uint64_t min_count, uint64_t *out_s,
+                                 uint64_t *out_e, uint64_t *out_count, uint64_t *out_len) {
+  if (int rc = check_replicas(idx, ndev)) return rc;
+  if (npat == 0) return FMX_OK;
+  if (!pat_off) return fail_arg("pat_off is NULL");
+  return run_shards(ndev, [&](uint32_t r) -> int {
+    uint64_t a, b;
+    fmx_shard_range(npat, ndev, r, &a, &b);
+    if (b == a) return FMX_OK;
+    // entries a .. b of the caller's offsets with the caller's pattern buffer, as fmx_count_batch_multi
+    return fmx_suffix_match_batch(idx[r], pat, pat_off + a, b - a, s0e0 ? s0e0 + 2 * a : nullptr, min_count,
+                                  out_s ? out_s + a : nullptr, out_e ? out_e + a : nullptr,
+                                  out_count ? out_count + a : nullptr, out_len ? out_len + a : nullptr);
+  });
+}
+
 int fmx_count_batch_multi_resident(fmx_index *const *idx, uint32_t ndev, const void *const *d_pat,
                                    const uint64_t *const *d_pat_off, uint64_t npat, const uint64_t *const *d_s0e0,
                                    uint64_t *out_s, uint64_t *out_e, uint64_t *out_count) {

@@ -2789,6 +2789,8 @@ int fmx_launch_count(const fmx_index *idx, const void *d_pat, const uint64_t *d_
   return FMX_OK;
 }
 
+#include "fmx_suffix.h"     // fmx_launch_suffix_match: the longest-suffix-match twins of the count kernels
+
 uint64_t fmx_offsets_tile_bytes(uint64_t npat) {
   uint64_t ntiles = (npat + FMX_SCAN_TILE - 1) / FMX_SCAN_TILE;
   if (ntiles == 0) ntiles = 1;

@@ -2098,6 +2098,8 @@ int fmxw_launch_count(const fmx_index *idx, const void *d_pat, const uint64_t *d
   return FMX_OK;
 }
 
+#include "fmx_wide_suffix.h"   // fmxw_launch_suffix_match: the longest-suffix-match twins of the count kernels
+
 // fills table[code] for every k-mer code of a wide index (FMX_FLAG_KMER_TABLE; the rank structures must be complete)
 int fmxw_launch_kmer_build(const fmx_index *idx, FmxWideKmer *d_table, uint32_t k, uint32_t bits, hipStream_t st) {
   const FmxWideDev w = idx->wide;

@@ -114,6 +114,23 @@ class Index {
     check(fmx_count_batch(h_, flat.data(), off.data(), patterns.size(), nullptr, s.data(), e.data(),
                           nullptr));
   }
+  // batched: the longest suffix of patterns[k] whose interval keeps >= min_count rows (0 = 1) -> that (s, e) and its
+  // length (fmx_suffix_match_batch; a symbol above max_character ends the match, it is no error)
+  void suffix_match_many(const std::vector<std::vector<uint8_t>> &patterns, uint64_t min_count, std::vector<uint64_t> &s,
+                         std::vector<uint64_t> &e, std::vector<uint64_t> &lengths) const {
+    std::vector<uint8_t> flat;
+    std::vector<uint64_t> off(1, 0);
+    for (auto &p : patterns) {
+      flat.insert(flat.end(), p.begin(), p.end());
+      off.push_back(flat.size());
+    }
+    if (flat.empty()) flat.push_back(0);
+    s.assign(patterns.size(), 0);
+    e.assign(patterns.size(), 0);
+    lengths.assign(patterns.size(), 0);
+    check(fmx_suffix_match_batch(h_, flat.data(), off.data(), patterns.size(), nullptr, min_count, s.data(), e.data(),
+                                 nullptr, lengths.data()));
+  }
   // fmx_replicate: a second index with its own copy of the HBM arrays on `device` (no rebuild)
   std::unique_ptr<Index> replicate(int device) const {
     fmx_index *h = nullptr;

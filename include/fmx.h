@@ -257,6 +257,32 @@ int fmx_count_batch(const fmx_index *idx, const void *pat, const uint64_t *pat_o
 /* sticky device-side status of *_dev calls on this handle; reading clears it */
 int fmx_stream_status(const fmx_index *idx);
 
+/* ---- longest suffix of a pattern that occurs: its interval and its length ---- */
+/* An ADDITION with no counterpart in the crate; the closest is Search::search (wrapper.rs:99-124) repeated one
+ * symbol at a time until count() falls below min_count.  For pattern k = pat[pat_off[k] .. pat_off[k+1]) and
+ * `min_count` (0 is treated as 1):
+ *     (s, e) = s0e0 ? (s0e0[2k], s0e0[2k+1]) : (0, len);  L = 0
+ *     for c in pattern reversed:
+ *         if c > max_character: break                 # an absent symbol ends the match; NOT an error here
+ *         s' = lf_map2(c, s); e' = lf_map2(c, e)
+ *         if e' - s' < min_count: break               # min_count = 1  <=>  s' == e'
+ *         s = s'; e = e'; L += 1
+ *     out_s[k] = s; out_e[k] = e; out_count[k] = e - s; out_len[k] = L
+ * The interval is that of the last L symbols of the pattern (prepended to the start pair when `s0e0` is given) and
+ * is never emptier than the start pair.  An empty pattern, a start pair already below min_count and an empty text
+ * give L = 0 and the start pair.  So does a given start pair with e < s: it holds no row, out_count is 0 (on every
+ * index kind and both engines).  Symbol 0 is an ordinary symbol.  A pattern symbol > max_character does NOT set
+ * FMX_ERR_SYMBOL_RANGE (fmx_count_batch does): it ends that pattern's match.  Bad offsets and an `s0e0` entry above
+ * len() are FMX_ERR_ARG exactly as in fmx_count_batch (such a pattern is never read, its outputs are 0).  Any of the
+ * four output arrays may be NULL.  The results feed fmx_locate_batch unchanged: the positions are the occurrences of
+ * the matched suffix.  The dev form is asynchronous and reports through fmx_stream_status(). */
+int fmx_suffix_match_batch_dev(const fmx_index *idx, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat,
+                               const uint64_t *d_s0e0, uint64_t min_count, uint64_t *d_out_s, uint64_t *d_out_e,
+                               uint64_t *d_out_count, uint64_t *d_out_len, void *stream);
+int fmx_suffix_match_batch(const fmx_index *idx, const void *pat, const uint64_t *pat_off, uint64_t npat,
+                           const uint64_t *s0e0, uint64_t min_count, uint64_t *out_s, uint64_t *out_e,
+                           uint64_t *out_count, uint64_t *out_len);
+
 /* ---- Search::iter_matches().map(MatchWithLocate::locate) ------------------ */
 /* (wrapper.rs:137-139, 203-217, 238-242 -> fm_index.rs:127-140, sample.rs:46-60)
  *     out_pos[out_off[k] + j] = get_sa(s[k] + j),  j = 0 .. e[k]-s[k]-1
@@ -314,6 +340,10 @@ void fmx_shard_range(uint64_t nitems, uint32_t nshards, uint32_t r, uint64_t *be
 int fmx_count_batch_multi(fmx_index *const *idx, uint32_t ndev, const void *pat, const uint64_t *pat_off,
                           uint64_t npat, const uint64_t *s0e0, uint64_t *out_s, uint64_t *out_e,
                           uint64_t *out_count);
+/* fmx_suffix_match_batch over `ndev` replicas: same arguments (HOST pointers), same results, same errors */
+int fmx_suffix_match_batch_multi(fmx_index *const *idx, uint32_t ndev, const void *pat, const uint64_t *pat_off,
+                                 uint64_t npat, const uint64_t *s0e0, uint64_t min_count, uint64_t *out_s,
+                                 uint64_t *out_e, uint64_t *out_count, uint64_t *out_len);
 /* the same with every shard's patterns already RESIDENT on its device, results into HOST arrays -- the measurement
  * protocol of SURVEY section 8d ("exclude ... H2D upload from both sides; include D2H of results on the GPU side";
  * benches/count.rs:29-37 times results the caller can read).  d_pat[r] / d_pat_off[r] / d_s0e0[r] (nullable array,

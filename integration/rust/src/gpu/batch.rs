@@ -47,6 +47,39 @@ impl<C: GpuCharacter> GpuBackend<C> {
         BatchCounts { s, e, counts }
     }
 
+    /// The longest suffix of every pattern whose interval keeps at least `min_count` rows (0 = 1): that interval and
+    /// its length, in one call.  No counterpart in the crate -- it replaces refining a `Search` one symbol at a
+    /// time (`wrapper.rs:99-124`) until `count()` drops.  A symbol above `max_character` ends a pattern's match.
+    pub fn suffix_match_many<P: AsRef<[C]>>(&self, patterns: &[P], min_count: u64) -> (BatchCounts, Vec<u64>) {
+        let mut flat: Vec<C> = Vec::new();
+        let mut off = Vec::with_capacity(patterns.len() + 1);
+        off.push(0u64);
+        for p in patterns {
+            flat.extend_from_slice(p.as_ref());
+            off.push(flat.len() as u64);
+        }
+        let n = patterns.len();
+        let (mut s, mut e, mut counts, mut lengths) = (vec![0u64; n], vec![0u64; n], vec![0u64; n], vec![0u64; n]);
+        let rc = unsafe {
+            ffi::fmx_suffix_match_batch(
+                self.h,
+                flat.as_ptr() as *const _,
+                off.as_ptr(),
+                n as u64,
+                std::ptr::null(),
+                min_count,
+                s.as_mut_ptr(),
+                e.as_mut_ptr(),
+                counts.as_mut_ptr(),
+                lengths.as_mut_ptr(),
+            )
+        };
+        if rc != ffi::FMX_OK {
+            panic!("libfmx: {}", last_error());
+        }
+        (BatchCounts { s, e, counts }, lengths)
+    }
+
     /// every match position of every pattern of a `search_many` result
     pub fn locate_many(&self, found: &BatchCounts) -> BatchPositions {
         let n = found.s.len();
