@@ -21,7 +21,7 @@ from . import _lib as L
 
 __all__ = ["Text", "Error", "FMIndex", "FMIndexWithLocate", "RLFMIndex", "RLFMIndexWithLocate",
            "FMIndexMultiPieces", "FMIndexMultiPiecesWithLocate", "Search", "Match", "SearchBatch",
-           "Replicas", "pack_patterns"]
+           "MismatchBatch", "Replicas", "pack_patterns"]
 
 
 class Error(Exception):
@@ -217,6 +217,28 @@ class _Index:
         SearchBatch of that interval with `.lengths` (numpy u64), so `.locate()` gives the seed positions.  A symbol
         above max_character ends a pattern's match and is no error."""
         return _suffix_match(self, self._lib.fmx_suffix_match_batch, (self._h,), patterns, flat, off, s0e0, min_count)
+
+    def mismatch_search_many(self, patterns=None, flat=None, off=None, s0e0=None, max_mismatches=1):
+        """every interval of a variant of each pattern with at most `max_mismatches` (0, 1 or 2) substituted symbols,
+        in the order of include/fmx.h (fmx_mismatch_count_batch, the scan, fmx_mismatch_search_batch): a MismatchBatch.
+        Symbol 0 is never substituted in; a symbol above max_character costs one substitution and is no error."""
+        if flat is None:
+            flat, off = pack_patterns(patterns, self._dtype)
+        flat = _sym(flat, self._dtype)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        npat = len(off) - 1
+        se = None if s0e0 is None else np.ascontiguousarray(s0e0, dtype=np.uint64)
+        nint, cnt = (np.zeros(max(npat, 1), dtype=np.uint64) for _ in range(2))
+        _check(self._lib.fmx_mismatch_count_batch(self._h, _p(flat), _p(off), npat, _p(se), int(max_mismatches),
+                                                  _p(nint), _p(cnt)))
+        ooff = np.zeros(npat + 1, dtype=np.uint64)
+        ooff[1:] = np.cumsum(nint[:npat], dtype=np.uint64)
+        total = int(ooff[-1])
+        s, e = (np.zeros(max(total, 1), dtype=np.uint64) for _ in range(2))
+        ed = np.full(2 * max(total, 1), 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)
+        _check(self._lib.fmx_mismatch_search_batch(self._h, _p(flat), _p(off), npat, _p(se), int(max_mismatches),
+                                                   _p(ooff), total, _p(s), _p(e), _p(ed)))
+        return MismatchBatch(self, cnt[:npat], nint[:npat], ooff, s[:total], e[:total], ed[:2 * total])
 
     def locate_many(self, s, e):
         """(offsets u64[npat+1], positions u64[total]) in the reference's iteration order."""
@@ -576,6 +598,34 @@ class Match:
             for c in syms[0]:
                 yield int(c)
             i = int(nxt[0])
+
+
+class MismatchBatch:
+    """Result of mismatch_search_many.  Per pattern: `counts` (occurrences within the Hamming distance), `nint`
+    (intervals) and `off` (npat + 1: the intervals of pattern k are off[k] .. off[k+1]).  Per interval: `s`, `e` and
+    `edits`, a masked (total, 2) array of (pos, sym) records -- the substitutions in the order they were made (the one
+    nearer the pattern's end first; pos from the pattern's start, sym the text's symbol there), masked where unused."""
+
+    def __init__(self, index, counts, nint, off, s, e, edit_words):
+        self._ix = index
+        self.counts = counts
+        self.nint = nint
+        self.off = off
+        self.s = s
+        self.e = e
+        w = edit_words.reshape(-1, 2)
+        rec = np.zeros(w.shape, dtype=[("pos", np.uint64), ("sym", np.uint64)])
+        unused = w == np.uint64(0xFFFFFFFFFFFFFFFF)
+        rec["pos"] = np.where(unused, 0, w >> np.uint64(32))
+        rec["sym"] = np.where(unused, 0, w & np.uint64(0xFFFFFFFF))
+        self.edits = np.ma.masked_array(rec, mask=unused)
+
+    def count(self):
+        return self.counts
+
+    def locate(self):
+        """(offsets u64[total + 1], positions u64[hits]): the positions of every interval (fmx_locate_batch)"""
+        return self._ix.locate_many(self.s, self.e)
 
 
 class SearchBatch:

@@ -75,6 +75,10 @@ SYMBOLS = [
     ("fmx_stream_status", _I, [_V]),
     ("fmx_suffix_match_batch_dev", _I, [_V, _V, _V, _U64, _V, _U64, _V, _V, _V, _V, _V]),
     ("fmx_suffix_match_batch", _I, [_V, _V, _V, _U64, _V, _U64, _V, _V, _V, _V]),
+    ("fmx_mismatch_count_batch_dev", _I, [_V, _V, _V, _U64, _V, _U32, _V, _V, _V]),
+    ("fmx_mismatch_count_batch", _I, [_V, _V, _V, _U64, _V, _U32, _V, _V]),
+    ("fmx_mismatch_search_batch_dev", _I, [_V, _V, _V, _U64, _V, _U32, _V, _U64, _V, _V, _V, _V]),
+    ("fmx_mismatch_search_batch", _I, [_V, _V, _V, _U64, _V, _U32, _V, _U64, _V, _V, _V]),
     ("fmx_locate_batch_dev", _I, [_V, _V, _V, _U64, _V, _U64, _V, _V]),
     ("fmx_locate_batch", _I, [_V, _V, _V, _U64, _V, _V]),
     ("fmx_offsets_dev", _I, [_V, _V, _V, _U64, _V, _V]),

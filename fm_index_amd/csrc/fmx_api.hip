@@ -385,6 +385,31 @@ int fmx_suffix_match_batch_dev(const fmx_index *idx, const void *d_pat, const ui
   return fmx_launch_suffix_match(idx, d_pat, d_pat_off, npat, d_s0e0, min_count, d_out_s, d_out_e, d_out_count,
                                  d_out_len, (hipStream_t)stream);
 }
+// what both passes and both forms of the mismatch search refuse before anything is launched
+#define CHECK_MISMATCH(idx, max_mismatches)                                                              \
+  if ((max_mismatches) > FMX_MAX_MISMATCHES) return fail(FMX_ERR_ARG, "max_mismatches exceeds FMX_MAX_MISMATCHES"); \
+  if ((idx)->is_wide)                                                                                    \
+    return fail(FMX_ERR_UNSUPPORTED, "the mismatch search is not available on the 64-bit engine (n >= 2^32 - 16 or FMX_FLAG_FORCE_WIDE)")
+int fmx_mismatch_count_batch_dev(const fmx_index *idx, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat,
+                                 const uint64_t *d_s0e0, uint32_t max_mismatches, uint64_t *d_out_nint,
+                                 uint64_t *d_out_count, void *stream) {
+  CHECK_IDX(idx);
+  CHECK_MISMATCH(idx, max_mismatches);
+  if (npat && (!d_pat_off)) return fail(FMX_ERR_ARG, "pat_off is NULL");
+  return fmx_launch_mismatch(idx, d_pat, d_pat_off, npat, d_s0e0, max_mismatches, false, nullptr, 0, d_out_nint,
+                             d_out_count, nullptr, nullptr, nullptr, (hipStream_t)stream);
+}
+int fmx_mismatch_search_batch_dev(const fmx_index *idx, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat,
+                                  const uint64_t *d_s0e0, uint32_t max_mismatches, const uint64_t *d_out_off,
+                                  uint64_t total_intervals, uint64_t *d_out_s, uint64_t *d_out_e,
+                                  uint64_t *d_out_edit, void *stream) {
+  CHECK_IDX(idx);
+  CHECK_MISMATCH(idx, max_mismatches);
+  if (npat && (!d_pat_off)) return fail(FMX_ERR_ARG, "pat_off is NULL");
+  if (npat && (!d_out_off)) return fail(FMX_ERR_ARG, "out_off is NULL");
+  return fmx_launch_mismatch(idx, d_pat, d_pat_off, npat, d_s0e0, max_mismatches, true, d_out_off, total_intervals,
+                             nullptr, nullptr, d_out_s, d_out_e, d_out_edit, (hipStream_t)stream);
+}
 int fmx_offsets_dev(const fmx_index *idx, const uint64_t *d_s, const uint64_t *d_e, uint64_t npat,
                     uint64_t *d_out_off, void *stream) {
   CHECK_IDX(idx);
@@ -1107,6 +1132,79 @@ int fmx_suffix_match_batch(const fmx_index *idx, const void *pat, const uint64_t
   if (out_count) FMX_HIP(hipMemcpyAsync(out_count, d_c, b_out, hipMemcpyDeviceToHost, S));
   if (out_len) FMX_HIP(hipMemcpyAsync(out_len, d_l, b_out, hipMemcpyDeviceToHost, S));
   return finish_host_call(sx);
+}
+// The two passes of the mismatch search on host arrays: upload, one launch, download, like fmx_suffix_match_batch.
+// write = false: out_a / out_b = out_nint / out_count (npat entries).  write = true: out_a / out_b / out_edit = out_s /
+// out_e (total entries) / out_edit (2 * total); the device copies START as the caller's arrays, so that a slot no
+// pattern may write comes back as it was.
+static int mismatch_host(const fmx_index *idx, const void *pat, const uint64_t *pat_off, uint64_t npat,
+                         const uint64_t *s0e0, uint32_t max_mismatches, bool write, const uint64_t *out_off,
+                         uint64_t total, uint64_t *out_a, uint64_t *out_b, uint64_t *out_edit) {
+  CHECK_IDX(idx);
+  CHECK_MISMATCH(idx, max_mismatches);
+  if (npat == 0) return FMX_OK;
+  if (!pat_off) return fail(FMX_ERR_ARG, "pat_off is NULL");
+  if (write && !out_off) return fail(FMX_ERR_ARG, "out_off is NULL");
+  const uint64_t ptotal = pat_off[npat], first = pat_off[0];
+  if (first > ptotal) return fail(FMX_ERR_ARG, "pat_off is not non-decreasing");
+  const uint64_t span = ptotal - first;
+  if (span && !pat) return fail(FMX_ERR_ARG, "pat is NULL");
+  const uint32_t sb = idx->sym_bytes;  // device symbol width
+  std::vector<uint32_t> narrow;
+  const uint8_t *src = (const uint8_t *)pat + first * sb;        // the first symbol this call reads
+  if (idx->sym_bytes_abi == 8 && span) {  // u64 patterns: narrow, saturating so out-of-range stays out of range
+    narrow.resize((size_t)span);
+    const uint64_t *p64 = (const uint64_t *)pat + first;
+    for (uint64_t i = 0; i < span; i++) narrow[i] = p64[i] > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)p64[i];
+    src = (const uint8_t *)narrow.data();
+  }
+  const size_t b_pat = (size_t)span * sb, b_pp = (size_t)npat * 8, b_off = (size_t)(npat + 1) * 8;
+  const size_t b_out = write ? (size_t)total * 8 : b_pp;         // one of the two main output arrays
+  HostCall hc;
+  FMX_HIP(hc.open(idx->device, HostCall::pad(b_pat + 32) + HostCall::pad(b_off) + (s0e0 ? HostCall::pad(2 * b_pp) : 0) +
+                                   (write ? HostCall::pad(b_off) + 256 + HostCall::pad(2 * b_out) : 0) +
+                                   2 * (HostCall::pad(b_out) + 256)));
+  uint8_t *d_pat = hc.take<uint8_t>(b_pat + 32);
+  uint64_t *d_off = hc.take<uint64_t>(b_off);
+  uint64_t *d_se = s0e0 ? hc.take<uint64_t>(2 * b_pp) : nullptr;
+  uint64_t *d_oo = write ? hc.take<uint64_t>(b_off) : nullptr;
+  uint64_t *d_a = hc.take<uint64_t>(b_out), *d_b = hc.take<uint64_t>(b_out);
+  uint64_t *d_ed = write ? hc.take<uint64_t>(2 * b_out) : nullptr;
+  SmallCtx *sx = hc.sx;
+  hipStream_t S = sx->st;
+  CallStatus cs(sx);
+  FMX_HIP(hipMemsetAsync(status_dev(sx), 0, 4, S));
+  if (b_pat) FMX_HIP(hipMemcpyAsync(d_pat, src, b_pat, hipMemcpyHostToDevice, S));
+  FMX_HIP(hipMemcpyAsync(d_off, pat_off, b_off, hipMemcpyHostToDevice, S));
+  if (s0e0) FMX_HIP(hipMemcpyAsync(d_se, s0e0, 2 * b_pp, hipMemcpyHostToDevice, S));
+  if (write) {
+    FMX_HIP(hipMemcpyAsync(d_oo, out_off, b_off, hipMemcpyHostToDevice, S));
+    if (out_a && b_out) FMX_HIP(hipMemcpyAsync(d_a, out_a, b_out, hipMemcpyHostToDevice, S));
+    if (out_b && b_out) FMX_HIP(hipMemcpyAsync(d_b, out_b, b_out, hipMemcpyHostToDevice, S));
+    if (out_edit && b_out) FMX_HIP(hipMemcpyAsync(d_ed, out_edit, 2 * b_out, hipMemcpyHostToDevice, S));
+  }
+  // (virtual: symbol 0 of the caller's buffer -- never dereferenced below symbol `first`)
+  if (int rc = fmx_launch_mismatch(idx, d_pat - first * sb, d_off, npat, d_se, max_mismatches, write, d_oo, total,
+                                   !write && out_a ? d_a : nullptr, !write && out_b ? d_b : nullptr,
+                                   write && out_a ? d_a : nullptr, write && out_b ? d_b : nullptr,
+                                   out_edit ? d_ed : nullptr, S)) {
+    (void)hipStreamSynchronize(S);
+    return rc;
+  }
+  if (out_a && b_out) FMX_HIP(hipMemcpyAsync(out_a, d_a, b_out, hipMemcpyDeviceToHost, S));
+  if (out_b && b_out) FMX_HIP(hipMemcpyAsync(out_b, d_b, b_out, hipMemcpyDeviceToHost, S));
+  if (out_edit && b_out) FMX_HIP(hipMemcpyAsync(out_edit, d_ed, 2 * b_out, hipMemcpyDeviceToHost, S));
+  return finish_host_call(sx);
+}
+int fmx_mismatch_count_batch(const fmx_index *idx, const void *pat, const uint64_t *pat_off, uint64_t npat,
+                             const uint64_t *s0e0, uint32_t max_mismatches, uint64_t *out_nint, uint64_t *out_count) {
+  return mismatch_host(idx, pat, pat_off, npat, s0e0, max_mismatches, false, nullptr, 0, out_nint, out_count, nullptr);
+}
+int fmx_mismatch_search_batch(const fmx_index *idx, const void *pat, const uint64_t *pat_off, uint64_t npat,
+                              const uint64_t *s0e0, uint32_t max_mismatches, const uint64_t *out_off,
+                              uint64_t total_intervals, uint64_t *out_s, uint64_t *out_e, uint64_t *out_edit) {
+  return mismatch_host(idx, pat, pat_off, npat, s0e0, max_mismatches, true, out_off, total_intervals, out_s, out_e,
+                       out_edit);
 }
 void fmx_set_error_text(const char *text) { g_last_error = text ? text : ""; }
 

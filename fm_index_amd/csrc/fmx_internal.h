@@ -390,6 +390,14 @@ int fmx_launch_count(const fmx_index *idx, const void *d_pat, const uint64_t *d_
 int fmx_launch_suffix_match(const fmx_index *idx, const void *d_pat, const uint64_t *d_off, uint64_t npat,
                             const uint64_t *d_s0e0, uint64_t min_count, uint64_t *d_s, uint64_t *d_e,
                             uint64_t *d_cnt, uint64_t *d_len, hipStream_t st);
+// backward search with up to max_mismatches (<= FMX_MAX_MISMATCHES) substitutions, 32-bit engine only (fmx_mismatch.h).
+// write = false: pass 1, d_nint[k] / d_cnt[k] = intervals emitted / their rows; write = true: pass 2, interval j of
+// pattern k to slot d_out_off[k] + j of d_s / d_e / d_edit (2 entries per slot), never outside the pattern's own
+// slots below `total`.  Any output may be NULL.
+int fmx_launch_mismatch(const fmx_index *idx, const void *d_pat, const uint64_t *d_off, uint64_t npat,
+                        const uint64_t *d_s0e0, uint32_t max_mismatches, bool write, const uint64_t *d_out_off,
+                        uint64_t total, uint64_t *d_nint, uint64_t *d_cnt, uint64_t *d_s, uint64_t *d_e,
+                        uint64_t *d_edit, hipStream_t st);
 // rows_ws / tile_ws: caller-provided scratch (fmx_locate_rows_bytes / fmx_offsets_tile_bytes); NULL = take
 // it from the stream-ordered allocator for the duration of the call
 int fmx_launch_locate(const fmx_index *idx, const uint64_t *d_s, const uint64_t *d_e,

@@ -17,7 +17,8 @@
  *    positions and samples) for every kind, with or without locate (u8 / u16 / u32 symbols, max_character < 2^26;
  *    FMX_KIND_FM over u8 with max_character <= 7 -- DNA -- has the faster one-level kernels): every entry point
  *    works on it (build, count, locate, offsets, the trait calls, piece ids and match rows of a multi-pieces index,
- *    extract, save / load, the exports -- the samples through fmx_export_sa_samples64) except fmx_export_sa.  Of the
+ *    extract, save / load, the exports -- the samples through fmx_export_sa_samples64) except fmx_export_sa and the
+ *    mismatch search (fmx_mismatch_*_batch*: FMX_ERR_UNSUPPORTED).  Of the
  *    opt-in accelerators it honours FMX_FLAG_KMER_TABLE and FMX_FLAG_PAIR_INDEX (below; the pair index on FMX_KIND_FM
  *    over u8 symbols with max_character <= 4, n >= 4 and no interior zero, for +1 byte per symbol), and the default
  *    index of a text that long gets neither (both are by request only on this engine).
@@ -282,6 +283,66 @@ int fmx_suffix_match_batch_dev(const fmx_index *idx, const void *d_pat, const ui
 int fmx_suffix_match_batch(const fmx_index *idx, const void *pat, const uint64_t *pat_off, uint64_t npat,
                            const uint64_t *s0e0, uint64_t min_count, uint64_t *out_s, uint64_t *out_e,
                            uint64_t *out_count, uint64_t *out_len);
+
+/* ---- backward search with up to two substituted symbols ---- */
+/* An ADDITION with no counterpart in the crate; the closest is Search::search (wrapper.rs:99-124) on every variant of
+ * the pattern that differs from it in at most `max_mismatches` symbols.  For pattern P = pat[pat_off[k] ..
+ * pat_off[k+1]) of m symbols and budget K = max_mismatches (0, 1 or 2):
+ *     enum(i, s, e, d):                      # i symbols still to prepend, d substitutions spent
+ *         if i == 0: emit (s, e, edits); return
+ *         p = P[i-1]
+ *         if d < K:
+ *             for c = 1 .. max_character ascending, c != p:
+ *                 s' = lf_map2(c, s); e' = lf_map2(c, e)
+ *                 if e' > s': enum(i-1, s', e', d+1)   # edit (pos = i-1, sym = c) appended
+ *         if p <= max_character:
+ *             s' = lf_map2(p, s); e' = lf_map2(p, e)
+ *             if e' > s': enum(i-1, s', e', d)
+ *     start: (s, e) = s0e0 ? (s0e0[2k], s0e0[2k+1]) : (0, len);  if e > s: enum(m, s, e, 0)
+ * The intervals emitted for pattern k, in exactly this order, are its result: substitutions at a position come before
+ * the pattern's own symbol, positions go from the back of the pattern, the exact match (if any) comes last.  The
+ * emitted strings are distinct and equally long, so their intervals are disjoint and their sizes add up to the number
+ * of occurrences within Hamming distance K.  Symbol 0 is never substituted IN (a mismatch may not consume a sentinel
+ * or a piece separator); a 0 in the pattern itself is an ordinary symbol (on a multi-pieces index lf_map2(0, .) can
+ * give e' < s': no row).  A pattern symbol > max_character is no error here (it is in fmx_count_batch, as it is not in
+ * fmx_suffix_match_batch): it cannot match, so it costs one substitution where it stands, and with K = 0 such a
+ * pattern has no interval.  An empty pattern emits the start pair if it holds a row; an empty text, or a start pair
+ * with e <= s, emits nothing.  Bad offsets and an `s0e0` entry above len() are FMX_ERR_ARG exactly as in
+ * fmx_count_batch (such a pattern is never read and has no interval); max_mismatches > FMX_MAX_MISMATCHES is
+ * FMX_ERR_ARG before anything is launched.
+ *
+ * Two passes, as with locate.  Pass 1 (fmx_mismatch_count_batch*): out_nint[k] = number of intervals emitted,
+ * out_count[k] = the sum of their sizes; either may be NULL.  out_off = the exclusive scan of out_nint, npat + 1
+ * entries -- fmx_offsets_dev with an all-zero d_s and d_e = out_nint makes it.  Pass 2 (fmx_mismatch_search_batch*):
+ * interval j of pattern k goes to slot out_off[k] + j of out_s / out_e, and its substitutions to out_edit, which has
+ * 2 * total_intervals entries: slot 2j + t holds the t-th substitution in the order it was made (the one nearer the
+ * pattern's end first) as (pos << 32) | sym -- pos counts from the pattern's start, sym is the text's symbol at that
+ * position -- and an unused slot holds UINT64_MAX.  Any output array may be NULL.  out_s / out_e feed
+ * fmx_locate_batch unchanged.  Pass 2 is safe against offsets that do not fit: a pattern writes only slots in
+ * [out_off[k], min(out_off[k+1], total_intervals)), and if it emits more or fewer intervals than its slots the call
+ * reports FMX_ERR_ARG; nothing outside that range is ever written.
+ *
+ * Engines: the 32-bit engine serves every index kind (FMIndex, RLFMIndex, multi-pieces; with or without locate; u8 /
+ * u16 / u32 symbols).  Indexes with the pair index or the k-mer table are served from their plain records -- the
+ * accelerators cannot place a mismatch inside a pair or a k-mer -- so the results are identical with and without
+ * FMX_FLAG_PLAIN.  One-level DNA-like indexes (the indexes fmx_count_batch serves one 128-byte line per step) rank
+ * every symbol of a position from the two lines the exact step loads anyway; every other index pays one lf_map2 pair
+ * per candidate symbol, so its cost grows with the alphabet (symbols that do not occur in the text are skipped).  A
+ * handle of the wide (64-bit) engine returns FMX_ERR_UNSUPPORTED with a message in fmx_last_error() and writes
+ * nothing.  The dev forms are asynchronous and report through fmx_stream_status(). */
+#define FMX_MAX_MISMATCHES 2
+int fmx_mismatch_count_batch_dev(const fmx_index *idx, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat,
+                                 const uint64_t *d_s0e0, uint32_t max_mismatches, uint64_t *d_out_nint,
+                                 uint64_t *d_out_count, void *stream);
+int fmx_mismatch_count_batch(const fmx_index *idx, const void *pat, const uint64_t *pat_off, uint64_t npat,
+                             const uint64_t *s0e0, uint32_t max_mismatches, uint64_t *out_nint, uint64_t *out_count);
+int fmx_mismatch_search_batch_dev(const fmx_index *idx, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat,
+                                  const uint64_t *d_s0e0, uint32_t max_mismatches, const uint64_t *d_out_off,
+                                  uint64_t total_intervals, uint64_t *d_out_s, uint64_t *d_out_e,
+                                  uint64_t *d_out_edit, void *stream);
+int fmx_mismatch_search_batch(const fmx_index *idx, const void *pat, const uint64_t *pat_off, uint64_t npat,
+                              const uint64_t *s0e0, uint32_t max_mismatches, const uint64_t *out_off,
+                              uint64_t total_intervals, uint64_t *out_s, uint64_t *out_e, uint64_t *out_edit);
 
 /* ---- Search::iter_matches().map(MatchWithLocate::locate) ------------------ */
 /* (wrapper.rs:137-139, 203-217, 238-242 -> fm_index.rs:127-140, sample.rs:46-60)
