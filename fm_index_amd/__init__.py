@@ -21,7 +21,7 @@ from . import _lib as L
 
 __all__ = ["Text", "Error", "FMIndex", "FMIndexWithLocate", "RLFMIndex", "RLFMIndexWithLocate",
            "FMIndexMultiPieces", "FMIndexMultiPiecesWithLocate", "Search", "Match", "SearchBatch",
-           "MismatchBatch", "Replicas", "pack_patterns"]
+           "MismatchBatch", "MatchStatsBatch", "Replicas", "pack_patterns"]
 
 
 class Error(Exception):
@@ -239,6 +239,24 @@ class _Index:
         _check(self._lib.fmx_mismatch_search_batch(self._h, _p(flat), _p(off), npat, _p(se), int(max_mismatches),
                                                    _p(ooff), total, _p(s), _p(e), _p(ed)))
         return MismatchBatch(self, cnt[:npat], nint[:npat], ooff, s[:total], e[:total], ed[:2 * total])
+
+    def match_stats_many(self, patterns=None, flat=None, off=None, min_count=1, max_len=0, min_seed_len=0):
+        """backward matching statistics of every pattern (fmx_match_stats_batch): for every end position the longest
+        suffix of that prefix whose interval keeps >= min_count rows (at most max_len symbols, 0 = no cap), one entry
+        per pattern symbol: a MatchStatsBatch.  min_seed_len > 0 keeps the interval only where the match is a seed (at
+        least that long and not contained in a longer match of its pattern): `.seeds()` are the super-maximal exact
+        matches.  A symbol above max_character ends a match and is no error."""
+        if flat is None:
+            flat, off = pack_patterns(patterns, self._dtype)
+        flat = _sym(flat, self._dtype)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        npat = len(off) - 1
+        total = int(off[-1] - off[0]) if npat > 0 and off[-1] >= off[0] else 0
+        s, e, ln = (np.zeros(max(total, 1), dtype=np.uint64) for _ in range(3))
+        _check(self._lib.fmx_match_stats_batch(self._h, _p(flat), _p(off), npat, int(min_count), int(max_len),
+                                               int(min_seed_len), _p(s), _p(e), _p(ln)))
+        return MatchStatsBatch(self, off - off[0] if npat > 0 else np.zeros(1, dtype=np.uint64), ln[:total],
+                               s[:total], e[:total])
 
     def locate_many(self, s, e):
         """(offsets u64[npat+1], positions u64[total]) in the reference's iteration order."""
@@ -626,6 +644,38 @@ class MismatchBatch:
     def locate(self):
         """(offsets u64[total + 1], positions u64[hits]): the positions of every interval (fmx_locate_batch)"""
         return self._ix.locate_many(self.s, self.e)
+
+
+class MatchStatsBatch:
+    """Result of match_stats_many.  `offsets` (npat + 1): the slots of pattern k are offsets[k] .. offsets[k+1], one per
+    pattern symbol; slot offsets[k] + i - 1 is end position i.  Per slot: `lengths` (the matching statistic) and `s`,
+    `e` (the interval of that match; (0, 0) where the length is 0 or the seed filter dropped the slot)."""
+
+    def __init__(self, index, offsets, lengths, s, e):
+        self._ix = index
+        self.offsets = offsets
+        self.lengths = lengths
+        self.s = s
+        self.e = e
+
+    def seeds(self):
+        """structured array (pattern, begin, length, s, e) of the slots with e > s, in slot order: the match of such a
+        slot is pattern[begin : begin + length]"""
+        t = np.nonzero(self.e > self.s)[0].astype(np.uint64)
+        out = np.zeros(len(t), dtype=[(f, np.uint64) for f in ("pattern", "begin", "length", "s", "e")])
+        k = np.searchsorted(self.offsets, t, side="right").astype(np.uint64) - np.uint64(1)
+        out["pattern"] = k
+        out["length"] = self.lengths[t]
+        out["begin"] = t - self.offsets[k] + np.uint64(1) - self.lengths[t]
+        out["s"] = self.s[t]
+        out["e"] = self.e[t]
+        return out
+
+    def locate(self):
+        """(offsets u64[nseeds + 1], positions u64[hits]): the text positions of every seed of `.seeds()`, in its order
+        (fmx_locate_batch)"""
+        sd = self.seeds()
+        return self._ix.locate_many(sd["s"], sd["e"])
 
 
 class SearchBatch:

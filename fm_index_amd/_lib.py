@@ -79,6 +79,8 @@ SYMBOLS = [
     ("fmx_mismatch_count_batch", _I, [_V, _V, _V, _U64, _V, _U32, _V, _V]),
     ("fmx_mismatch_search_batch_dev", _I, [_V, _V, _V, _U64, _V, _U32, _V, _U64, _V, _V, _V, _V]),
     ("fmx_mismatch_search_batch", _I, [_V, _V, _V, _U64, _V, _U32, _V, _U64, _V, _V, _V]),
+    ("fmx_match_stats_batch_dev", _I, [_V, _V, _V, _U64, _U64, _U64, _U64, _U64, _V, _V, _V, _V]),
+    ("fmx_match_stats_batch", _I, [_V, _V, _V, _U64, _U64, _U64, _U64, _V, _V, _V]),
     ("fmx_locate_batch_dev", _I, [_V, _V, _V, _U64, _V, _U64, _V, _V]),
     ("fmx_locate_batch", _I, [_V, _V, _V, _U64, _V, _V]),
     ("fmx_offsets_dev", _I, [_V, _V, _V, _U64, _V, _V]),

@@ -410,6 +410,28 @@ int fmx_mismatch_search_batch_dev(const fmx_index *idx, const void *d_pat, const
   return fmx_launch_mismatch(idx, d_pat, d_pat_off, npat, d_s0e0, max_mismatches, true, d_out_off, total_intervals,
                              nullptr, nullptr, d_out_s, d_out_e, d_out_edit, (hipStream_t)stream);
 }
+// what both forms of the matching statistics refuse before anything is launched
+#define CHECK_MATCH_STATS(idx, out_len)                                                                  \
+  if ((idx)->is_wide)                                                                                    \
+    return fail(FMX_ERR_UNSUPPORTED, "the matching statistics are not available on the 64-bit engine (n >= 2^32 - 16 or FMX_FLAG_FORCE_WIDE)"); \
+  if (!(out_len)) return fail(FMX_ERR_ARG, "out_len is NULL")
+int fmx_match_stats_batch_dev(const fmx_index *idx, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat,
+                              uint64_t total_syms, uint64_t min_count, uint64_t max_len, uint64_t min_seed_len,
+                              uint64_t *d_out_s, uint64_t *d_out_e, uint64_t *d_out_len, void *stream) {
+  CHECK_IDX(idx);
+  CHECK_MATCH_STATS(idx, d_out_len);
+  if (npat == 0) {                                   // no pattern owns a slot: all of them are empty
+    if (total_syms == 0) return FMX_OK;
+    const size_t b = (size_t)total_syms * 8;
+    if (d_out_s) FMX_HIP(hipMemsetAsync(d_out_s, 0, b, (hipStream_t)stream));
+    if (d_out_e) FMX_HIP(hipMemsetAsync(d_out_e, 0, b, (hipStream_t)stream));
+    FMX_HIP(hipMemsetAsync(d_out_len, 0, b, (hipStream_t)stream));
+    return fail(FMX_ERR_ARG, "total_syms is not pat_off[npat] - pat_off[0]");
+  }
+  if (!d_pat_off) return fail(FMX_ERR_ARG, "pat_off is NULL");
+  return fmx_launch_match_stats(idx, d_pat, d_pat_off, npat, total_syms, min_count, max_len, min_seed_len, d_out_s,
+                                d_out_e, d_out_len, (hipStream_t)stream);
+}
 int fmx_offsets_dev(const fmx_index *idx, const uint64_t *d_s, const uint64_t *d_e, uint64_t npat,
                     uint64_t *d_out_off, void *stream) {
   CHECK_IDX(idx);
@@ -1205,6 +1227,51 @@ int fmx_mismatch_search_batch(const fmx_index *idx, const void *pat, const uint6
                               uint64_t total_intervals, uint64_t *out_s, uint64_t *out_e, uint64_t *out_edit) {
   return mismatch_host(idx, pat, pat_off, npat, s0e0, max_mismatches, true, out_off, total_intervals, out_s, out_e,
                        out_edit);
+}
+// The matching statistics on host arrays: upload, the same kernels, download, like fmx_suffix_match_batch; the output
+// arrays have one entry per pattern symbol of pat[pat_off[0] .. pat_off[npat]).
+int fmx_match_stats_batch(const fmx_index *idx, const void *pat, const uint64_t *pat_off, uint64_t npat,
+                          uint64_t min_count, uint64_t max_len, uint64_t min_seed_len, uint64_t *out_s,
+                          uint64_t *out_e, uint64_t *out_len) {
+  CHECK_IDX(idx);
+  CHECK_MATCH_STATS(idx, out_len);
+  if (npat == 0) return FMX_OK;
+  if (!pat_off) return fail(FMX_ERR_ARG, "pat_off is NULL");
+  const uint64_t total = pat_off[npat], first = pat_off[0];
+  if (first > total) return fail(FMX_ERR_ARG, "pat_off is not non-decreasing");
+  const uint64_t span = total - first;
+  if (span && !pat) return fail(FMX_ERR_ARG, "pat is NULL");
+  const uint32_t sb = idx->sym_bytes;  // device symbol width
+  std::vector<uint32_t> narrow;
+  const uint8_t *src = (const uint8_t *)pat + first * sb;        // the first symbol this call reads
+  if (idx->sym_bytes_abi == 8 && span) {  // u64 patterns: narrow, saturating so out-of-range stays out of range
+    narrow.resize((size_t)span);
+    const uint64_t *p64 = (const uint64_t *)pat + first;
+    for (uint64_t i = 0; i < span; i++) narrow[i] = p64[i] > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)p64[i];
+    src = (const uint8_t *)narrow.data();
+  }
+  const size_t b_pat = (size_t)span * sb, b_out = (size_t)span * 8, b_off = (size_t)(npat + 1) * 8;
+  HostCall hc;
+  FMX_HIP(hc.open(idx->device, HostCall::pad(b_pat + 32) + HostCall::pad(b_off) + 3 * (HostCall::pad(b_out) + 256)));
+  uint8_t *d_pat = hc.take<uint8_t>(b_pat + 32);
+  uint64_t *d_off = hc.take<uint64_t>(b_off);
+  uint64_t *d_s = hc.take<uint64_t>(b_out), *d_e = hc.take<uint64_t>(b_out), *d_l = hc.take<uint64_t>(b_out);
+  SmallCtx *sx = hc.sx;
+  hipStream_t S = sx->st;
+  CallStatus cs(sx);
+  FMX_HIP(hipMemsetAsync(status_dev(sx), 0, 4, S));
+  if (b_pat) FMX_HIP(hipMemcpyAsync(d_pat, src, b_pat, hipMemcpyHostToDevice, S));
+  FMX_HIP(hipMemcpyAsync(d_off, pat_off, b_off, hipMemcpyHostToDevice, S));
+  // (virtual: symbol 0 of the caller's buffer -- never dereferenced below symbol `first`)
+  if (int rc = fmx_launch_match_stats(idx, d_pat - first * sb, d_off, npat, span, min_count, max_len, min_seed_len,
+                                      out_s ? d_s : nullptr, out_e ? d_e : nullptr, d_l, S)) {
+    (void)hipStreamSynchronize(S);
+    return rc;
+  }
+  if (out_s && b_out) FMX_HIP(hipMemcpyAsync(out_s, d_s, b_out, hipMemcpyDeviceToHost, S));
+  if (out_e && b_out) FMX_HIP(hipMemcpyAsync(out_e, d_e, b_out, hipMemcpyDeviceToHost, S));
+  if (b_out) FMX_HIP(hipMemcpyAsync(out_len, d_l, b_out, hipMemcpyDeviceToHost, S));
+  return finish_host_call(sx);
 }
 void fmx_set_error_text(const char *text) { g_last_error = text ? text : ""; }
 

@@ -398,6 +398,13 @@ int fmx_launch_mismatch(const fmx_index *idx, const void *d_pat, const uint64_t 
                         const uint64_t *d_s0e0, uint32_t max_mismatches, bool write, const uint64_t *d_out_off,
                         uint64_t total, uint64_t *d_nint, uint64_t *d_cnt, uint64_t *d_s, uint64_t *d_e,
                         uint64_t *d_edit, hipStream_t st);
+// backward matching statistics, 32-bit engine only (fmx_mstats.h): for every end position of every pattern (slot t, one
+// per pattern symbol, `total` of them) the longest suffix of that prefix with >= min_count rows (0 = 1), at most
+// max_len symbols (0 = no cap); min_seed_len > 0 keeps (s, e) only where the match is a seed.  d_len must be given
+// (it carries the owner ids between the kernels); d_s / d_e may be NULL.  npat > 0.
+int fmx_launch_match_stats(const fmx_index *idx, const void *d_pat, const uint64_t *d_off, uint64_t npat,
+                           uint64_t total, uint64_t min_count, uint64_t max_len, uint64_t min_seed_len,
+                           uint64_t *d_s, uint64_t *d_e, uint64_t *d_len, hipStream_t st);
 // rows_ws / tile_ws: caller-provided scratch (fmx_locate_rows_bytes / fmx_offsets_tile_bytes); NULL = take
 // it from the stream-ordered allocator for the duration of the call
 int fmx_launch_locate(const fmx_index *idx, const uint64_t *d_s, const uint64_t *d_e,

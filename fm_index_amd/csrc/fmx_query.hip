@@ -2791,6 +2791,7 @@ int fmx_launch_count(const fmx_index *idx, const void *d_pat, const uint64_t *d_
 
 #include "fmx_suffix.h"     // fmx_launch_suffix_match: the longest-suffix-match twins of the count kernels
 #include "fmx_mismatch.h"   // fmx_launch_mismatch: backward search with up to FMX_MAX_MISMATCHES substitutions
+#include "fmx_mstats.h"     // fmx_launch_match_stats: matching statistics of every pattern prefix, and the seed filter
 
 uint64_t fmx_offsets_tile_bytes(uint64_t npat) {
   uint64_t ntiles = (npat + FMX_SCAN_TILE - 1) / FMX_SCAN_TILE;

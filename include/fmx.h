@@ -344,6 +344,54 @@ int fmx_mismatch_search_batch(const fmx_index *idx, const void *pat, const uint6
                               const uint64_t *s0e0, uint32_t max_mismatches, const uint64_t *out_off,
                               uint64_t total_intervals, uint64_t *out_s, uint64_t *out_e, uint64_t *out_edit);
 
+/* ---- backward matching statistics and super-maximal exact-match seeds ---- */
+/* An ADDITION with no counterpart in the crate: fmx_suffix_match_batch asked at EVERY end position of every pattern,
+ * without copying the prefixes.  Pattern k = pat[pat_off[k] .. pat_off[k+1]) has m symbols; end position i (1 <= i <=
+ * m) is the prefix P[0 .. i), and its SLOT is t = pat_off[k] - pat_off[0] + i - 1.  The three output arrays have
+ * total_syms = pat_off[npat] - pat_off[0] entries, one per pattern symbol.  For every slot, with `min_count` (0 is
+ * treated as 1) and `max_len` (0 = no cap):
+ *     (s, e) = (0, len);  L = 0                       # no s0e0: every end position starts from the whole index
+ *     for c in P[0 .. i) reversed:
+ *         if L == max_len (max_len != 0): break
+ *         if c > max_character: break                 # an absent symbol ends the match; NOT an error here
+ *         s' = lf_map2(c, s); e' = lf_map2(c, e)
+ *         if e' < s' or e' - s' < min_count: break
+ *         s = s'; e = e'; L += 1
+ *     out_len[t] = L;  (out_s[t], out_e[t]) = L > 0 ? (s, e) : (0, 0)
+ * out_len[t] is the backward matching statistic: the length of the longest suffix of P[0 .. i) that occurs at least
+ * min_count times (and is no longer than max_len).  A slot with L == 0 holds (0, 0), not the start pair, so the arrays
+ * feed fmx_offsets_dev and fmx_locate_batch unchanged (npat = total_syms there) and an empty slot costs nothing.
+ * Symbol 0 is an ordinary symbol.
+ *
+ * max_len bounds the work of a slot at max_len steps; without it a pattern that is a long substring of the text costs
+ * O(m^2) steps.  With max_len == min_seed_len == w the call returns every w-mer of the pattern that occurs (at least
+ * min_count times): the slots with out_e > out_s.
+ *
+ * min_seed_len > 0 turns on the seed filter: slot t of pattern k keeps its (s, e) only if out_len[t] >= min_seed_len
+ * and (i == m or out_len[t+1] <= out_len[t]); every other slot gets (0, 0).  out_len stays the raw statistic either
+ * way.  Where lf_map2 is monotone (everything but symbol 0 on a multi-pieces index) the kept slots are exactly the
+ * matches of the pattern that are not contained in a longer one, the super-maximal exact matches: "occurs at least
+ * min_count times" is closed under taking substrings, so L[i+1] <= L[i] + 1 and the starts i - L[i] never decrease; a
+ * match ending at i can therefore only be contained in the one ending at i + 1, and it is exactly when L[i+1] ==
+ * L[i] + 1.  The seed of slot t begins at symbol i - L of its pattern and is L symbols long.
+ *
+ * out_len == NULL is FMX_ERR_ARG before anything is launched (it is the result, and the call keeps its own state in
+ * it between its kernels); out_s and out_e may be NULL.  Bad offsets (going backwards, leaving [pat_off[0],
+ * pat_off[npat]), a pattern longer than 2^32 - 1) are FMX_ERR_ARG exactly as in fmx_count_batch, and so is
+ * pat_off[npat] - pat_off[0] != total_syms.  Such a pattern is never read; its slots, and every slot no valid pattern
+ * owns, hold L = 0 and (0, 0) (where bad offsets make two valid patterns overlap, a shared slot is answered for one of
+ * them).  Nothing outside [0, total_syms) of any output array is ever written, whatever the offsets say.  An empty
+ * text, npat == 0 and total_syms == 0 are fine.  A handle of the wide (64-bit) engine returns FMX_ERR_UNSUPPORTED with
+ * a message in fmx_last_error() and writes nothing.  The dev form is asynchronous and reports through
+ * fmx_stream_status(); it allocates nothing and does not synchronise (kernels and hipMemsetAsync on `stream` only), so
+ * it can be captured into a hipGraph.  The host form uploads, runs the same kernels and synchronises. */
+int fmx_match_stats_batch_dev(const fmx_index *idx, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat,
+                              uint64_t total_syms, uint64_t min_count, uint64_t max_len, uint64_t min_seed_len,
+                              uint64_t *d_out_s, uint64_t *d_out_e, uint64_t *d_out_len, void *stream);
+int fmx_match_stats_batch(const fmx_index *idx, const void *pat, const uint64_t *pat_off, uint64_t npat,
+                          uint64_t min_count, uint64_t max_len, uint64_t min_seed_len,
+                          uint64_t *out_s, uint64_t *out_e, uint64_t *out_len);
+
 /* ---- Search::iter_matches().map(MatchWithLocate::locate) ------------------ */
 /* (wrapper.rs:137-139, 203-217, 238-242 -> fm_index.rs:127-140, sample.rs:46-60)
  *     out_pos[out_off[k] + j] = get_sa(s[k] + j),  j = 0 .. e[k]-s[k]-1
