@@ -117,6 +117,52 @@ __device__ __forceinline__ bool fmx_kmer_code_lane(const uint8_t *__restrict__ p
   return bad == 0u;
 }
 
+// ---- the unread end of a pattern in registers (fmx_count_pair_kernel) ----
+// The group reads the last min(j, 32) unread symbols of pat[pbeg, pbeg + j) at once (j > 0): lane g takes the symbols at
+// distance g, g + 8, g + 16, g + 24 from the unread end -- four byte loads, all issued before one wait; a distance
+// beyond the pattern's start is clamped onto its first symbol and the value discarded, so nothing outside
+// [pbeg, pbeg + j) is read.  sym[] receives the lane's four raw symbols.  When every symbol read is in 1..lim
+// (lim <= 4) the window is PACKED: the symbol at distance t as the 2-bit code c - 1 in bits [2t, 2t + 2) of `win`, so
+// that a pair step's record code (c1 - 1) * 4 + (c2 - 1) is win & 15.  Returns false otherwise (win is then unusable).
+__device__ __forceinline__ bool fmx_load_sym_window(const uint8_t *__restrict__ pat, uint64_t pbeg, uint32_t j,
+                                                    uint32_t lim, uint32_t g, uint64_t &win, uint32_t (&sym)[4]) {
+  const uint8_t *last = pat + pbeg + (j - 1u);          // distance 0
+#pragma unroll
+  for (uint32_t h = 0; h < 4; h++) {
+    const uint32_t t = g + 8u * h;
+    sym[h] = *(last - (t < j ? t : j - 1u));
+  }
+  uint32_t lo = 0, hi = 0, bad = 0;
+#pragma unroll
+  for (uint32_t h = 0; h < 4; h++) {
+    const uint32_t t = g + 8u * h, cc = sym[h] - 1u;
+    const bool live = t < j;
+    bad |= (uint32_t)(live && cc >= lim);
+    const uint32_t f = live ? (cc & 3u) << (2u * (t & 15u)) : 0u;
+    if (h < 2) lo |= f; else hi |= f;
+  }
+  bad = fmx_group_sum(bad);
+  win = ((uint64_t)fmx_group_sum(hi) << 32) | fmx_group_sum(lo);   // disjoint bit fields: sum == or
+  return bad == 0u;
+}
+// fmx_kmer_code of the window's first kk (<= 16, <= symbols in the window) symbols for a table of 2-bit codes: the
+// table wants distance 0 in the TOP bits, so the 2-bit fields of the low word are reversed (bit reversal, then the
+// two bits of every field swapped back) and the fields beyond kk shifted out
+__device__ __forceinline__ uint32_t fmx_window_kmer_code2(uint64_t win, uint32_t kk) {
+  uint32_t r = __brev((uint32_t)win);
+  r = ((r & 0x55555555u) << 1) | ((r >> 1) & 0x55555555u);
+  return r >> (32u - 2u * kk);
+}
+// ... and for any other code width, from the lanes' own symbols at distance g and g + 8 (fmx_kmer_code without its
+// loads; the caller knows that all kk symbols are in 1..max_character)
+__device__ __forceinline__ uint32_t fmx_window_kmer_code(uint32_t sym0, uint32_t sym1, uint32_t kk, uint32_t bits,
+                                                         uint32_t g) {
+  uint32_t part = 0;
+  if (g < kk) part = ((sym0 - 1u) & ((1u << bits) - 1u)) << (bits * (kk - 1u - g));
+  if (g + 8u < kk) part |= ((sym1 - 1u) & ((1u << bits) - 1u)) << (bits * (kk - 9u - g));
+  return fmx_group_sum(part);
+}
+
 // value of lane (4 * (lane / 4) + q) for the four lanes of a quad (DPP quad_perm [q,q,q,q])
 template <int QQ>
 __device__ __forceinline__ uint32_t fmx_quad_bcast_c(uint32_t v) {

@@ -320,16 +320,25 @@ __global__ __launch_bounds__(FMX_BLOCK) void fmx_count_f3_kernel(
 // collapses the interval, the single step for the LAST symbol decides whether the reference
 // would have stopped after one symbol (then ITS (s, e) is returned) or after two.
 // ---------------------------------------------------------------------------
-// (Round 6 measured two ways of putting more requests in flight per wave here -- the kernel runs at 0.68 of the request
-// ceiling where the plain kernel reaches 0.93, three of a pattern's ~13 dependent round trips being its start: offsets,
-// the k-mer code's symbols, the table entry -- and dropped both (profiles/r06/pair_kernel_ab.txt; this kernel: 0.324 ms
-// per 2^20 x 32 symbols): two patterns per group with the record loads of both issued before one wait, 0.42 ms
-// (0.52 with one pattern in that form: loads and rank decode in separate loops cost more than the second chain
-// brings); a pattern as a state machine whose start stages take one round each like a step, every load of a round
-// issued before one wait, 0.50-0.64 ms -- the groups of a wave sit in different stages, their loads serialise on shared
-// destination registers or take the kernel to 104 VGPRs, and the divergent round costs more than it hides.)
+// Shape (unchanged since round 6, whose attempts to put more requests in flight per wave all lost 25-60 %:
+// profiles/r06/pair_kernel_ab.txt): 8-lane groups, one pattern per group at a time, one loop iteration per step.
+// Round 7 removed work inside that shape (profiles/r07/pair_start_isa.md, pair_start_ab.txt: 0.324 -> 0.314 ms per
+// 2^20 x 32 symbols):
+//   * a pattern's unread end lives in registers: the group reads up to 32 symbols at once (fmx_load_sym_window, four
+//     byte loads per lane before one wait) and packs them as 2-bit codes, so a step takes its record code from
+//     `win & 15` and issues no byte loads; the k-mer code comes out of the same window.  A window that holds a symbol
+//     outside 1..min(4, max_character) is not packed: the rest of that pattern runs on the byte-wise step (`slow`),
+//     which reads c2 / c1 when it needs them -- FMX_ERR_SYMBOL_RANGE is raised when a bad symbol is REACHED, symbol 0,
+//     the single step for an odd remainder and the collapsed-pair rule are the byte-wise code's.
+//   * from the end of one pattern to the first record load of the next a group passes two full waits (window, table
+//     entry), not five: the next pattern's offsets are taken over before the finished pattern's results are stored.
+// SGPRs: the kernel must start 8 waves per SIMD -- the grid is 65 536 groups = 8 waves on each of the 1024 SIMDs, and
+// with 7 resident the eighth runs as a second round (measured: 0.39 ms at 88 SGPRs, mean 4.3 waves per SIMD).  The
+// compiler's own occupancy figure still says 8 there; the hardware's allocation (16-register granules, plus VCC, the
+// flat-scratch pair and the trap handler's 16) does not.  The parent sat at 74, exactly on the limit; the cap below
+// keeps this kernel under it (the values it displaces are loop invariants of the pattern start, kept in VGPR lanes).
 template <bool KM>
-__global__ __launch_bounds__(FMX_BLOCK) void fmx_count_pair_kernel(
+__global__ __launch_bounds__(FMX_BLOCK) __attribute__((amdgpu_num_sgpr(80))) void fmx_count_pair_kernel(
     const uint4 *__restrict__ rec1, const uint4 *__restrict__ rec2, uint32_t n,
     uint32_t max_character, uint32_t row0, uint32_t row1, uint32_t *status,
     const uint2 *__restrict__ kmer, uint32_t kmer_k, uint32_t kmer_bits,
@@ -342,28 +351,35 @@ __global__ __launch_bounds__(FMX_BLOCK) void fmx_count_pair_kernel(
 
   uint64_t k = gid;
   bool active = k < npat, fresh = true;
-  uint64_t pbeg = 0;
+  bool slow = false;         // this pattern's symbols are read byte by byte (its last window could not be packed)
+  uint64_t pbeg = 0, win = 0;
   uint32_t j = 0, s = 0, e = 0;
-  uint32_t c2 = 0, c1 = 0;   // c2 = last unread symbol, c1 = the one before it
+  uint32_t jw = 0;           // `win` holds the unread symbols [jw, j) of the pattern, the last one in its low bits
   uint32_t nsteps = 0;
+  const uint32_t lim = max_character < 4u ? max_character : 4u;   // a packed window holds symbols 1..lim only
   const uint64_t ptot = npat ? off[npat] : 0;   // symbols the caller declares behind `pat`
   const uint64_t pmin = npat ? off[0] : 0;      // ... starting at this symbol (a slice of a larger batch keeps its absolute offsets)
-  // the offsets of the group's NEXT pattern are requested when the current one starts (round 6): the start of a pattern
-  // is three dependent round trips -- offsets, the k-mer code's symbols, the table entry -- of its ~13, and this one
-  // travels under the current pattern's steps
-  uint64_t nbeg = active ? off[k] : 0, nend = active ? off[k + 1] : 0;
+  // the offsets of a group's pattern travel under the steps of the pattern before it (round 6): they are taken over
+  // when that pattern ENDS, before its results are stored (see there), and the offsets of pattern `kn`, the one after,
+  // are requested in the same place
+  // (one 16-byte value, loaded by one instruction into the registers it stays in: as two 8-byte values the compiler
+  // loads them into temporaries and copies them at the end of the block, behind a full wait)
+  typedef uint64_t fmx_u64x2 __attribute__((ext_vector_type(2), aligned(8)));
+  fmx_u64x2 noff = {0, 0};
+  if (active) noff = *(const fmx_u64x2 *)(off + k);
+  bool badoff = false;
+  auto take_offsets = [&](uint64_t kn) {
+    pbeg = noff.x;
+    const uint64_t pend = noff.y;
+    // offsets that go backwards or leave the pattern buffer: refuse, do not read (j = 0 from here on)
+    badoff = pend < pbeg || pbeg < pmin || pend > ptot || pend - pbeg > 0xFFFFFFFFull;
+    j = badoff ? 0u : (uint32_t)(pend - pbeg);
+    if (kn < npat) noff = *(const fmx_u64x2 *)(off + kn);
+  };
+  take_offsets(k + ngroups);
   while (active) {
     if (fresh) {
-      pbeg = nbeg;
-      const uint64_t pend = nend;
-      if (k + ngroups < npat) { nbeg = off[k + ngroups]; nend = off[k + ngroups + 1]; }
-      j = (uint32_t)(pend - pbeg);
-      // offsets that go backwards or leave the pattern buffer: refuse, do not read (j = 0 from here on)
-      const bool badoff = pend < pbeg || pbeg < pmin || pend > ptot || pend - pbeg > 0xFFFFFFFFull;
-      if (badoff) {
-        if (g == 0) atomicOr(status, 1u << FMX_ERR_ARG);
-        j = 0;
-      }
+      if (badoff && g == 0) atomicOr(status, 1u << FMX_ERR_ARG);
       if (s0e0) {
         const uint64_t s64 = s0e0[2 * k], e64 = s0e0[2 * k + 1];
         s = (uint32_t)s64;
@@ -375,35 +391,59 @@ __global__ __launch_bounds__(FMX_BLOCK) void fmx_count_pair_kernel(
       } else {
         s = 0;
         e = badoff ? 0u : n;
-        if (KM && j >= kmer_k) {                       // the first kmer_k steps from the table
-          uint32_t code;
-          if (fmx_kmer_code(pat, pbeg + j, kmer_k, kmer_bits, max_character, g, code)) {
-            FMX_TOUCH_G0N(g, &kmer[code]);
-            const uint2 se = kmer[code];
-            s = se.x;
-            e = se.y;
-            j = se.x == se.y ? 0u : j - kmer_k;        // empty already: the reference's break
-            nsteps += kmer_k;
-          }
+      }
+      slow = false;
+      jw = j;                                          // no window yet
+    }
+    // (re)fill the window: at the start of a pattern and whenever fewer than two of its symbols are left while the
+    // pattern has more -- one wait per 32 symbols
+    if (!slow && j - jw < 2u && jw != 0u) {
+      uint32_t sym[4];
+      const bool packed = fmx_load_sym_window(pat, pbeg, j, lim, g, win, sym);
+      slow = !packed;
+      jw = j > 32u ? j - 32u : 0u;
+      if (KM && fresh && !s0e0 && j >= kmer_k) {       // the first kmer_k steps from the table
+        uint32_t code;
+        bool ok = true;
+        if (packed) code = kmer_bits == 2u ? fmx_window_kmer_code2(win, kmer_k)
+                                           : fmx_window_kmer_code(sym[0], sym[1], kmer_k, kmer_bits, g);
+        else ok = fmx_kmer_code(pat, pbeg + j, kmer_k, kmer_bits, max_character, g, code);
+        if (ok) {
+          FMX_TOUCH_G0N(g, &kmer[code]);
+          const uint2 se = kmer[code];
+          s = se.x;
+          e = se.y;
+          j = se.x == se.y ? 0u : j - kmer_k;          // empty already: the reference's break
+          win >>= 2u * kmer_k;
+          nsteps += kmer_k;
         }
       }
-      c2 = j ? pat[pbeg + j - 1] : 0u;
-      c1 = j > 1 ? pat[pbeg + j - 2] : 0u;
-      fresh = false;
     }
+    fresh = false;
     bool done = (j == 0);
     if (!done) {
+      // c2 = last unread symbol, c1 = the one before it: a shift and a mask away in a packed window (whose symbols are
+      // all in 1..lim), two byte loads otherwise
+      uint32_t c2, code;
+      bool pair;
+      if (!slow) {
+        code = (uint32_t)win & 15u;
+        c2 = (code & 3u) + 1u;
+        pair = j - jw >= 2u;
+      } else {
+        c2 = pat[pbeg + j - 1];
+        const uint32_t c1 = j >= 2 ? pat[pbeg + j - 2] : 0u;
+        // (c1 in 1..lim, not 1..4: on an alphabet of fewer than four symbols a c1 above max_character must be reached
+        // as a c2 and refused there, as the plain kernel does; a pair step would answer it with an empty interval)
+        pair = j >= 2 && (c2 - 1u) < 4u && (c1 - 1u) < lim;
+        code = (c1 - 1u) * 4u + (c2 - 1u);
+      }
       if (c2 > max_character) {                        // reference: panic on cs[c]
         if (g == 0) atomicOr(status, 1u << FMX_ERR_SYMBOL_RANGE);
         s = 0; e = 0; done = true;
       } else {
-        const bool pair = j >= 2 && (c2 - 1u) < 4u && (c1 - 1u) < 4u;
-        // the two symbols after these ride along with the record loads
-        const uint32_t n1 = j > 2 ? pat[pbeg + j - 3] : 0u;
-        const uint32_t n2 = j > 3 ? pat[pbeg + j - 4] : 0u;
         uint32_t used;
         if (pair) {
-          const uint32_t code = (c1 - 1u) * 4u + (c2 - 1u);
           FMX_CHECK((s >> 7) < n / 128u + 1u && (e >> 7) < n / 128u + 1u);
           FMX_TOUCH_G0(g, &rec2[(size_t)(s >> 7) * 8u]);
           if ((e >> 7) != (s >> 7)) FMX_TOUCH_G0(g, &rec2[(size_t)(e >> 7) * 8u]);
@@ -441,11 +481,18 @@ __global__ __launch_bounds__(FMX_BLOCK) void fmx_count_pair_kernel(
         }
         nsteps += used;
         j -= used;
-        if (used == 2) { c2 = n1; c1 = n2; } else { c2 = c1; c1 = n1; }
+        win >>= 2u * used;
         if (s == e || j == 0) done = true;             // wrapper.rs:111-113
       }
     }
     if (done) {
+      // the next pattern's offsets are taken over BEFORE the result stores are issued: nothing else is in flight here
+      // (for a pattern that took no step, nothing but those offsets), while after the stores the wait for the offsets
+      // would be a wait for the stores' acknowledgements -- loads and stores share one counter.  The wait is explicit
+      // (s_waitcnt vmcnt(0), gfx9 encoding): without it the compiler is free to issue the stores first, and it waits
+      // again wherever a register of the offset loads is reused on a path it cannot rule out.
+      __builtin_amdgcn_s_waitcnt(0x0F70);
+      take_offsets(k + 2u * ngroups);
       if (g == 0) {
         if (out_s) out_s[k] = s;
         if (out_e) out_e[k] = e;
