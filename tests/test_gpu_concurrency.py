@@ -248,10 +248,11 @@ def test_large_host_pointer_batch_is_chunked_consistently():
 
 
 def test_page_locked_host_arrays_take_the_copy_kernel_pipeline():
-    """fmx_count_batch on page-locked caller arrays (torch pin_memory = hipHostMalloc): chunks are moved by copy
-    kernels over three streams.  Same answers as the pageable call for ragged patterns, with the caller's buffers
-    starting at odd bytes / odd words INSIDE their allocations (interior pointers, every alignment case of the
-    copy kernels), with refinement ranges, and with outputs the caller does not want (NULL)."""
+    """fmx_count_batch on page-locked caller arrays (torch pin_memory = hipHostMalloc): chunks are uploaded by DMA
+    copies and searched over three streams, and every search writes its results straight into the caller's arrays.
+    Same answers as the pageable call for ragged patterns, with the caller's buffers starting at odd bytes / odd
+    words INSIDE their allocations (interior pointers, every alignment the copies and the searches' writes can
+    meet), with refinement ranges, and with outputs the caller does not want (NULL)."""
     import torch
     lib = L.lib()
     t = W.dna_text_np(300000, 23)
