@@ -117,6 +117,14 @@ __device__ __forceinline__ bool fmx_kmer_code_lane(const uint8_t *__restrict__ p
   return bad == 0u;
 }
 
+// ---- pattern admission, both engines: the offsets of a pattern are checked before anything of it is read ----
+// Offsets that go backwards or leave the span [pmin, ptot) = [off[0], off[npat]) the caller declares behind `pat` (a
+// slice of a larger batch keeps its absolute offsets): such a pattern is refused and never read.  FMX_SPAN_BAD32 for
+// the 32-bit engine, which counts a pattern's symbols in 32 bits.  (Macros: the count kernels' instruction streams are
+// pinned, and the predicate reaches them unchanged only as text -- profiles/r12/kernel_regs.txt.)
+#define FMX_SPAN_BAD(pbeg, pend, pmin, ptot) ((pend) < (pbeg) || (pbeg) < (pmin) || (pend) > (ptot))
+#define FMX_SPAN_BAD32(pbeg, pend, pmin, ptot) \
+  (FMX_SPAN_BAD(pbeg, pend, pmin, ptot) || (pend) - (pbeg) > 0xFFFFFFFFull)
 // ---- the unread end of a pattern in registers (fmx_count_pair_kernel) ----
 // The group reads the last min(j, 32) unread symbols of pat[pbeg, pbeg + j) at once (j > 0): lane g takes the symbols at
 // distance g, g + 8, g + 16, g + 24 from the unread end -- four byte loads, all issued before one wait; a distance

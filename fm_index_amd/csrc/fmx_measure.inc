@@ -97,7 +97,7 @@ __global__ __launch_bounds__(FMX_BLOCK) void fmx_count_f3d_kernel(
       const uint64_t pend = off[k + 1];
       j = (uint32_t)(pend - pbeg);
       // offsets that go backwards or leave the pattern buffer: refuse, do not read (j = 0 from here on)
-      const bool badoff = pend < pbeg || pbeg < pmin || pend > ptot || pend - pbeg > 0xFFFFFFFFull;
+      const bool badoff = FMX_SPAN_BAD32(pbeg, pend, pmin, ptot);
       if (badoff) j = 0;
       bool bad = badoff;
       if (s0e0) {              // Search::search on an existing Search (wrapper.rs:105-106)
@@ -406,19 +406,20 @@ __global__ __launch_bounds__(FMX_LOC_BLOCK) void fmx_locate_f3w_kernel(
 }
 
 // count: returns true when an alternative kernel was launched
-static bool fmx_measure_count(const FmxCountCall &c, const FmxTune &tn, int sm) {
+static bool fmx_measure_count(const FmxCountCall &c, const FmxTune &tn, const FmxRoute &r) {
   const fmx_index *idx = c.idx;
   const FmxMwm &w = c.dv.bw;
   const bool dna = idx->kind == FMX_KIND_FM && idx->sym_bytes == 1 && w.nlevels == 1 && w.lv[0].fmt == 3;
   const bool pair = c.dv.pair_rec && idx->sym_bytes == 1 && tn.use_pair;
+  const int sm = fmx_select_mode(idx, c.dv);
   switch (tn.alt) {
-    case 100:  // generic kernels everywhere; RLFM per select structure
-      if (idx->kind == FMX_KIND_RLFM && sm == 1) { FMX_COUNT_KIND(c, FMX_KIND_RLFM, 1); return true; }
-      if (idx->kind == FMX_KIND_RLFM && sm == 2) { FMX_COUNT_KIND(c, FMX_KIND_RLFM, 2); return true; }
+    case 100:  // generic kernels everywhere; RLFM per select structure (instantiations only these builds have)
+      if (idx->kind == FMX_KIND_RLFM && sm == 1) { fmx_route_nl_km<FMX_KIND_RLFM, 1>(r, fmx_count_group(c)); return true; }
+      if (idx->kind == FMX_KIND_RLFM && sm == 2) { fmx_route_nl_km<FMX_KIND_RLFM, 2>(r, fmx_count_group(c)); return true; }
       return false;                                  // tn.generic steers the shipped dispatch
     case 20:   // endpoint per lane on an FM index
       if (idx->kind != FMX_KIND_FM || pair) return false;
-      FMX_EP_SM(c, fmx_ep_count_blocks(c.npat, tn.ep_blocks), FMX_KIND_FM, 0);
+      fmx_route_nl_km<FMX_KIND_FM, 0>(r, fmx_count_ep(c, fmx_ep_count_blocks(c.npat, tn.ep_blocks)));
       return true;
     default: break;
   }

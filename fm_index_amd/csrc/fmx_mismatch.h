@@ -31,7 +31,7 @@ __device__ __forceinline__ bool fmx_mm_begin(const uint64_t *__restrict__ off, c
   const uint64_t pend = off[k + 1];
   m = (uint32_t)(pend - pbeg);
   // offsets that go backwards or leave the pattern buffer: refuse, do not read
-  bool bad = pend < pbeg || pbeg < pmin || pend > ptot || pend - pbeg > 0xFFFFFFFFull;
+  bool bad = FMX_SPAN_BAD32(pbeg, pend, pmin, ptot);
   s = 0; e = n;
   if (s0e0) {
     const uint64_t s64 = s0e0[2 * k], e64 = s0e0[2 * k + 1];
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(FMX_BLOCK) void fmx_mm_empty_kernel(
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < npat; k += stride) {
     const uint64_t a = off[k], b = off[k + 1];
-    if (b < a || a < pmin || b > ptot || (s0e0 && (s0e0[2 * k] | s0e0[2 * k + 1]) != 0))
+    if (FMX_SPAN_BAD(a, b, pmin, ptot) || (s0e0 && (s0e0[2 * k] | s0e0[2 * k + 1]) != 0))
       atomicOr(status, 1u << FMX_ERR_ARG);
     FmxMmSlots sl{0, 0, 0};
     if (WRITE) sl = fmx_mm_slots(out_off, k, total);
@@ -323,48 +323,32 @@ struct FmxMmCall {
   uint32_t K; const uint64_t *out_off; uint64_t total; uint64_t *nint, *cnt, *s, *e, *edit; hipStream_t st;
   unsigned grid;
 };
-#define FMX_MM_F3_LAUNCH(c, KK, WR)                                                                   \
-  hipLaunchKernelGGL((fmx_mm_f3_kernel<KK, WR>), dim3((c).grid), dim3(FMX_BLOCK), 0, (c).st,            \
-                     (c).dv.bw.lv[0].rec, (c).dv.n, (c).dv.max_character, (c).dv.status,                \
-                     (const uint8_t *)(c).pat, (c).off, (c).npat, (c).s0e0, (c).out_off, (c).total,     \
-                     (c).nint, (c).cnt, (c).s, (c).e, (c).edit)
-#define FMX_MM_F3_K(c, WR)                                                                            \
-  do {                                                                                                \
-    if ((c).K == 0) FMX_MM_F3_LAUNCH(c, 0, WR);                                                       \
-    else if ((c).K == 1) FMX_MM_F3_LAUNCH(c, 1, WR);                                                  \
-    else FMX_MM_F3_LAUNCH(c, 2, WR);                                                                  \
-  } while (0)
-#define FMX_MM_LAUNCH(c, KIND, NL, SM, WR)                                                            \
-  hipLaunchKernelGGL((fmx_mm_kernel<KIND, NL, SM, WR>), dim3((c).grid), dim3(FMX_BLOCK), 0, (c).st,     \
-                     (c).dv, (c).pat, (c).off, (c).npat, (c).s0e0, (c).K, (c).out_off, (c).total,       \
-                     (c).nint, (c).cnt, (c).s, (c).e, (c).edit)
-#define FMX_MM_KIND(c, KIND, SM, WR)                                                                  \
-  do {                                                                                                \
-    if ((c).dv.bw.nlevels == 1) FMX_MM_LAUNCH(c, KIND, 1, SM, WR);                                    \
-    else if ((c).dv.bw.nlevels == 2) FMX_MM_LAUNCH(c, KIND, 2, SM, WR);                               \
-    else FMX_MM_LAUNCH(c, KIND, 0, SM, WR);                                                           \
-  } while (0)
-
-// the dispatch of fmx_launch_count without its accelerators: the one-level DNA kernel under the condition of
-// fmx_count_f3_kernel, else the group-per-pattern kernel of the index kind.  write = false: pass 1 (d_nint, d_cnt);
+// the ladder of fmx_route() (fmx_query.hip) without its accelerators and without the endpoint-per-lane shape: the
+// one-level DNA kernel, else the group-per-pattern kernel of the index kind.  write = false: pass 1 (d_nint, d_cnt);
 // write = true: pass 2 (d_out_off, total, d_s, d_e, d_edit).  The caller has refused K > FMX_MAX_MISMATCHES and
 // handles of the wide engine.
 template <bool WR>
 static int fmx_launch_mismatch_pass(const FmxMmCall &c) {
-  const fmx_index *idx = c.idx;
-  const FmxMwm &w = c.dv.bw;
-  if (idx->n == 0) {                                 // no record of any structure may be probed
-    hipLaunchKernelGGL(fmx_mm_empty_kernel<WR>, dim3(fmx_grid_for_groups((c.npat + 7) / 8)), dim3(FMX_BLOCK), 0, c.st,
+  const dim3 grid(c.grid), block(FMX_BLOCK);
+  if (c.idx->n == 0) {                               // no record of any structure may be probed
+    hipLaunchKernelGGL(fmx_mm_empty_kernel<WR>, dim3(fmx_grid_for_groups((c.npat + 7) / 8)), block, 0, c.st,
                        c.dv.status, c.off, c.npat, c.s0e0, c.out_off, c.total, c.nint, c.cnt);
-  } else if (idx->kind == FMX_KIND_FM && idx->sym_bytes == 1 && w.nlevels == 1 && w.lv[0].fmt == 3 &&
-             !fmx_tune().generic) {
-    FMX_MM_F3_K(c, WR);
-  } else if (idx->kind == FMX_KIND_FM) {
-    FMX_MM_KIND(c, FMX_KIND_FM, -1, WR);
-  } else if (idx->kind == FMX_KIND_MULTI) {
-    FMX_MM_KIND(c, FMX_KIND_MULTI, -1, WR);
+    FMX_HIP(hipGetLastError());
+    return FMX_OK;
+  }
+  const FmxRoute r = fmx_route(c.idx, c.dv, fmx_tune(), FMX_SHAPE_F3 | FMX_SHAPE_GROUP);
+  if (r.shape == FMX_SHAPE_F3) {
+    auto f3 = [&](auto kk) {
+      hipLaunchKernelGGL((fmx_mm_f3_kernel<kk(), WR>), grid, block, 0, c.st, c.dv.bw.lv[0].rec, c.dv.n,
+                         c.dv.max_character, c.dv.status, (const uint8_t *)c.pat, c.off, c.npat, c.s0e0, c.out_off,
+                         c.total, c.nint, c.cnt, c.s, c.e, c.edit);
+    };
+    if (c.K == 0) f3(FmxInt<0>{}); else if (c.K == 1) f3(FmxInt<1>{}); else f3(FmxInt<2>{});
   } else {
-    FMX_MM_KIND(c, FMX_KIND_RLFM, 0, WR);            // hints + record search: valid for every vector
+    fmx_route_group(r, [&](auto kind, auto nl, auto sm, auto) {
+      hipLaunchKernelGGL((fmx_mm_kernel<kind(), nl(), sm(), WR>), grid, block, 0, c.st, c.dv, c.pat, c.off, c.npat,
+                         c.s0e0, c.K, c.out_off, c.total, c.nint, c.cnt, c.s, c.e, c.edit);
+    });
   }
   FMX_HIP(hipGetLastError());
   return FMX_OK;

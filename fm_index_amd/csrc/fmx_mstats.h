@@ -20,9 +20,9 @@
 //      checks the offsets as the count kernels do and writes k into out_len[t] for the slots of valid patterns, below
 //      `total` only.  A group of the main kernel so learns its pattern from one read instead of a binary search of
 //      `off` per slot.
-//   2. the main kernel (one per count kernel shape that has a use here; 8-lane groups striding over the SLOTS, so the
-//      groups of a wave take adjacent end positions of one pattern and share its bytes and first record lines in
-//      cache) reads k = out_len[t], then off[k], and overwrites the slot with L.  An id that is no pattern's, or a slot
+//   2. the main kernel (one per rung of the dispatch ladder, fmx_route in fmx_query.hip, that has a use here; 8-lane
+//      groups striding over the SLOTS, so the groups of a wave take adjacent end positions of one pattern and share
+//      its bytes and first record lines in cache) reads k = out_len[t], then off[k], and overwrites the slot with L.  An id that is no pattern's, or a slot
 //      outside its pattern, is an unowned slot: zeros.  The kernel checks this itself and trusts nothing the owner
 //      pass wrote.  With the seed filter on, lane 0 also sets FMX_MS_LAST in the word of a pattern's last slot.
 //   3. fmx_ms_seed_kernel (elementwise; only with min_seed_len > 0 and out_s or out_e given) zeroes (s, e) of every
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(FMX_BLOCK) void fmx_ms_owner_kernel(
   if (gid == 0 && g == 0 && (ptot < pmin || ptot - pmin != total)) atomicOr(status, 1u << FMX_ERR_ARG);
   for (uint64_t k = gid; k < npat; k += ngroups) {
     const uint64_t pbeg = off[k], pend = off[k + 1];
-    if (pend < pbeg || pbeg < pmin || pend > ptot || pend - pbeg > 0xFFFFFFFFull) {
+    if (FMX_SPAN_BAD32(pbeg, pend, pmin, ptot)) {
       if (g == 0) atomicOr(status, 1u << FMX_ERR_ARG);
       continue;
     }
@@ -62,7 +62,7 @@ __device__ __forceinline__ bool fmx_ms_slot(const uint64_t *__restrict__ off, ui
   if (k >= npat) return false;
   pbeg = off[k];
   const uint64_t pend = off[k + 1];
-  if (pend < pbeg || pbeg < pmin || pend > ptot || pend - pbeg > 0xFFFFFFFFull) return false;
+  if (FMX_SPAN_BAD32(pbeg, pend, pmin, ptot)) return false;
   const uint64_t r = t + pmin - pbeg;                    // i - 1 (wraps to a huge value for a slot before the pattern)
   if (t + pmin < pbeg || r >= pend - pbeg) return false;
   i = (uint32_t)r + 1u;
@@ -345,43 +345,9 @@ __global__ __launch_bounds__(FMX_BLOCK) void fmx_ms_seed_kernel(
   }
 }
 
-// ---- launch ----
-struct FmxMsCall {
-  const fmx_index *idx; FmxDev dv; const void *pat; const uint64_t *off; uint64_t npat, total;
-  uint32_t mc, cap; uint64_t lastbit; uint64_t *s, *e, *len; hipStream_t st; bool km; unsigned grid;
-};
-#define FMX_MS_F3_LAUNCH(c, KM)                                                                      \
-  hipLaunchKernelGGL((fmx_ms_f3_kernel<KM>), dim3((c).grid), dim3(FMX_BLOCK), 0, (c).st,               \
-                     (c).dv.bw.lv[0].rec, (c).dv.n, (c).dv.max_character, (c).dv.kmer, (c).dv.kmer_k,  \
-                     (c).dv.kmer_bits, (const uint8_t *)(c).pat, (c).off, (c).npat, (c).total, (c).mc, \
-                     (c).cap, (c).lastbit, (c).s, (c).e, (c).len)
-#define FMX_MS_PAIR_LAUNCH(c, KM)                                                                    \
-  hipLaunchKernelGGL(fmx_ms_pair_kernel<KM>, dim3((c).grid), dim3(FMX_BLOCK), 0, (c).st,               \
-                     (c).dv.bw.lv[0].rec, (c).dv.pair_rec, (c).dv.n, (c).dv.max_character,             \
-                     (c).dv.pair_row0, (c).dv.pair_row1, (c).dv.kmer, (c).dv.kmer_k, (c).dv.kmer_bits, \
-                     (const uint8_t *)(c).pat, (c).off, (c).npat, (c).total, (c).mc, (c).cap,          \
-                     (c).lastbit, (c).s, (c).e, (c).len)
-#define FMX_MS_LAUNCH(c, KIND, NL, SM)                                                               \
-  do {                                                                                               \
-    if ((c).km && (c).idx->sym_bytes == 1)                                                           \
-      hipLaunchKernelGGL((fmx_ms_kernel<KIND, NL, true, SM>), dim3((c).grid), dim3(FMX_BLOCK), 0,      \
-                         (c).st, (c).dv, (c).pat, (c).off, (c).npat, (c).total, (c).mc, (c).cap,       \
-                         (c).lastbit, (c).s, (c).e, (c).len);                                        \
-    else                                                                                             \
-      hipLaunchKernelGGL((fmx_ms_kernel<KIND, NL, false, SM>), dim3((c).grid), dim3(FMX_BLOCK), 0,     \
-                         (c).st, (c).dv, (c).pat, (c).off, (c).npat, (c).total, (c).mc, (c).cap,       \
-                         (c).lastbit, (c).s, (c).e, (c).len);                                        \
-  } while (0)
-#define FMX_MS_KIND(c, KIND, SM)                                                                     \
-  do {                                                                                               \
-    if ((c).dv.bw.nlevels == 1) FMX_MS_LAUNCH(c, KIND, 1, SM);                                       \
-    else if ((c).dv.bw.nlevels == 2) FMX_MS_LAUNCH(c, KIND, 2, SM);                                  \
-    else FMX_MS_LAUNCH(c, KIND, 0, SM);                                                              \
-  } while (0)
-
-// the dispatch of fmx_launch_suffix_match minus the endpoint-per-lane shape (a run-length index takes the generic
-// kernel with hints + record search, which is valid for every vector).  The caller has refused a wide handle and a
-// NULL d_len; npat > 0.
+// ---- launch: the ladder of fmx_route() (fmx_query.hip) without the endpoint-per-lane shape -- a run-length index takes
+// the group kernel with hints + record search, which is valid for every vector.  The caller has refused a wide handle
+// and a NULL d_len; npat > 0. ----
 int fmx_launch_match_stats(const fmx_index *idx, const void *d_pat, const uint64_t *d_off, uint64_t npat,
                            uint64_t total, uint64_t min_count, uint64_t max_len, uint64_t min_seed_len,
                            uint64_t *d_s, uint64_t *d_e, uint64_t *d_len, hipStream_t st) {
@@ -399,23 +365,28 @@ int fmx_launch_match_stats(const fmx_index *idx, const void *d_pat, const uint64
     FMX_HIP(hipGetLastError());
     return FMX_OK;
   }
-  const FmxTune tn = fmx_tune();
-  const FmxMsCall c{idx, dv, d_pat, d_off, npat, total,
-                    min_count > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)min_count,
-                    (max_len == 0 || max_len > 0xFFFFFFFFull) ? 0xFFFFFFFFu : (uint32_t)max_len,
-                    seeds ? FMX_MS_LAST : 0ull, d_s, d_e, d_len, st, dv.kmer != nullptr && tn.use_kmer,
-                    fmx_grid_for_groups(total)};
-  const FmxMwm &w = dv.bw;
-  if (dv.pair_rec && idx->sym_bytes == 1 && tn.use_pair && !tn.generic) {
-    if (c.km) FMX_MS_PAIR_LAUNCH(c, true); else FMX_MS_PAIR_LAUNCH(c, false);
-  } else if (idx->kind == FMX_KIND_FM && idx->sym_bytes == 1 && w.nlevels == 1 && w.lv[0].fmt == 3 && !tn.generic) {
-    if (c.km) FMX_MS_F3_LAUNCH(c, true); else FMX_MS_F3_LAUNCH(c, false);
-  } else if (idx->kind == FMX_KIND_FM) {
-    FMX_MS_KIND(c, FMX_KIND_FM, -1);
-  } else if (idx->kind == FMX_KIND_MULTI) {
-    FMX_MS_KIND(c, FMX_KIND_MULTI, -1);
+  const FmxRoute r = fmx_route(idx, dv, fmx_tune(), FMX_SHAPE_PAIR | FMX_SHAPE_F3 | FMX_SHAPE_GROUP | FMX_HAS_KMER);
+  const uint32_t mc = min_count > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)min_count;
+  const uint32_t cap = (max_len == 0 || max_len > 0xFFFFFFFFull) ? 0xFFFFFFFFu : (uint32_t)max_len;
+  const uint64_t lastbit = seeds ? FMX_MS_LAST : 0ull;
+  const dim3 grid(fmx_grid_for_groups(total)), block(FMX_BLOCK);
+  const uint8_t *pat8 = (const uint8_t *)d_pat;
+  if (r.shape == FMX_SHAPE_PAIR) {
+    fmx_route_km(r, [&](auto km) {
+      hipLaunchKernelGGL(fmx_ms_pair_kernel<km()>, grid, block, 0, st, dv.bw.lv[0].rec, dv.pair_rec, dv.n,
+                         dv.max_character, dv.pair_row0, dv.pair_row1, dv.kmer, dv.kmer_k, dv.kmer_bits, pat8, d_off, npat,
+                         total, mc, cap, lastbit, d_s, d_e, d_len);
+    });
+  } else if (r.shape == FMX_SHAPE_F3) {
+    fmx_route_km(r, [&](auto km) {
+      hipLaunchKernelGGL(fmx_ms_f3_kernel<km()>, grid, block, 0, st, dv.bw.lv[0].rec, dv.n, dv.max_character, dv.kmer,
+                         dv.kmer_k, dv.kmer_bits, pat8, d_off, npat, total, mc, cap, lastbit, d_s, d_e, d_len);
+    });
   } else {
-    FMX_MS_KIND(c, FMX_KIND_RLFM, 0);                // hints + record search: valid for every vector
+    fmx_route_group(r, [&](auto kind, auto nl, auto sm, auto km) {
+      hipLaunchKernelGGL((fmx_ms_kernel<kind(), nl(), km(), sm()>), grid, block, 0, st, dv, d_pat, d_off, npat, total, mc,
+                         cap, lastbit, d_s, d_e, d_len);
+    });
   }
   FMX_HIP(hipGetLastError());
   if (seeds) {

@@ -14,6 +14,7 @@
 // large multi-level batches use one interval endpoint / one walk per lane (fmx_ep.h).
 // Integer / popcount / DPP work only; bound by HBM requests (count) and by the walk chain (locate).
 #include <cstdlib>
+#include <type_traits>
 #include "fmx_ep.h"
 
 #define FMX_BLOCK 256
@@ -87,7 +88,7 @@ __global__ __launch_bounds__(FMX_BLOCK, 8) void fmx_count_kernel(
       const uint64_t pend = off[k + 1];
       j = (uint32_t)(pend - pbeg);
       // offsets that go backwards or leave the pattern buffer: refuse, do not read (j = 0 from here on)
-      const bool badoff = pend < pbeg || pbeg < pmin || pend > ptot || pend - pbeg > 0xFFFFFFFFull;
+      const bool badoff = FMX_SPAN_BAD32(pbeg, pend, pmin, ptot);
       if (badoff) {
         if (g == 0) atomicOr(ix.status, 1u << FMX_ERR_ARG);
         j = 0;
@@ -162,7 +163,7 @@ __global__ __launch_bounds__(FMX_BLOCK) void fmx_count_empty_kernel(
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < npat; k += stride) {
     const uint64_t a = off[k], b = off[k + 1];
-    if (b < a || a < pmin || b > ptot || (s0e0 && (s0e0[2 * k] | s0e0[2 * k + 1]) != 0)) {
+    if (FMX_SPAN_BAD(a, b, pmin, ptot) || (s0e0 && (s0e0[2 * k] | s0e0[2 * k + 1]) != 0)) {
       atomicOr(status, 1u << FMX_ERR_ARG);
     } else if (b > a && fmx_load_sym(pat, sym_bytes, b - 1) > max_character) {   // the first step's cs[c]
       atomicOr(status, 1u << FMX_ERR_SYMBOL_RANGE);
@@ -217,7 +218,7 @@ __global__ __launch_bounds__(FMX_BLOCK) void fmx_count_f3_kernel(
         j[q] = (uint32_t)(pend - pbeg[q]);
         // offsets that go backwards or leave the pattern buffer: refuse, do not read (j = 0 from here on;
         // kept AHEAD of the table lookup: a trailing fix-up of (s, e, j) cost the pair kernel 30 %)
-        const bool badoff = pend < pbeg[q] || pbeg[q] < pmin || pend > ptot || pend - pbeg[q] > 0xFFFFFFFFull;
+        const bool badoff = FMX_SPAN_BAD32(pbeg[q], pend, pmin, ptot);
         if (badoff) {
           if (g == 0) atomicOr(status, 1u << FMX_ERR_ARG);
           j[q] = 0;
@@ -372,7 +373,7 @@ __global__ __launch_bounds__(FMX_BLOCK) __attribute__((amdgpu_num_sgpr(80))) voi
     pbeg = noff.x;
     const uint64_t pend = noff.y;
     // offsets that go backwards or leave the pattern buffer: refuse, do not read (j = 0 from here on)
-    badoff = pend < pbeg || pbeg < pmin || pend > ptot || pend - pbeg > 0xFFFFFFFFull;
+    badoff = FMX_SPAN_BAD32(pbeg, pend, pmin, ptot);
     j = badoff ? 0u : (uint32_t)(pend - pbeg);
     if (kn < npat) noff = *(const fmx_u64x2 *)(off + kn);
   };
@@ -542,7 +543,7 @@ __global__ __launch_bounds__(FMX_BLOCK) void fmx_count_ep_kernel(
       pbeg = off[k];
       const uint64_t pend = off[k + 1];
       j = (uint32_t)(pend - pbeg);
-      bool bad = pend < pbeg || pbeg < pmin || pend > ptot || pend - pbeg > 0xFFFFFFFFull;
+      bool bad = FMX_SPAN_BAD32(pbeg, pend, pmin, ptot);
       if (s0e0) {            // Search::search on an existing Search (wrapper.rs:105-106)
         const uint64_t mine = s0e0[2 * k + is_e], other = s0e0[2 * k + (is_e ^ 1u)];
         pos = (uint32_t)mine;
@@ -1946,7 +1947,7 @@ struct FmxTune {
 // everything a count / locate launch needs, for the launch helpers below and in fmx_measure.inc
 struct FmxCountCall {
   const fmx_index *idx; FmxDev dv; const void *pat; const uint64_t *off; uint64_t npat; const uint64_t *s0e0;
-  uint64_t *s, *e, *cnt, *steps; hipStream_t st; bool km; unsigned grid;
+  uint64_t *s, *e, *cnt, *steps; hipStream_t st; unsigned grid;
 };
 struct FmxLocateCall {
   const fmx_index *idx; FmxDev dv; uint64_t total; const uint32_t *rows; uint64_t *pos, *steps; hipStream_t st;
@@ -1966,55 +1967,110 @@ static inline int fmx_select_mode(const fmx_index *idx, const FmxDev &dv) {
   return idx->kind != FMX_KIND_RLFM ? -1 : (dv.b.pos && dv.bp.pos) ? 1 : (dv.b.dsel && dv.bp.dsel) ? 2 : 0;
 }
 
-// ---- count launch helpers (c = FmxCountCall) ----
+// ---------------------------------------------------------------------------
+// The dispatch ladder of the batched pattern queries: which kernel serves which index.  Written once for the four
+// families that share it -- count (below), longest-suffix match (fmx_suffix.h), matching statistics (fmx_mstats.h) and
+// mismatch search (fmx_mismatch.h).  fmx_route() reads the index and decides; fmx_route_ep() / fmx_route_group() /
+// fmx_route_km() turn the route's run-time values into template arguments; a family supplies its kernels and their
+// argument lists, and says which shapes it has -- a shape it lacks falls through to the next rung.
+// (The locate dispatch further down is a different ladder.)
+// ---------------------------------------------------------------------------
+enum FmxShape : unsigned {
+  FMX_SHAPE_PAIR = 1,    // opt-in pair index: two symbols per probe
+  FMX_SHAPE_F3 = 2,      // DNA (one 3-bit level): one 128-byte line per interval end and step, group per pattern
+  FMX_SHAPE_EP = 4,      // RLFM with a one-load select: an interval endpoint per lane (fmx_ep.h)
+  FMX_SHAPE_GROUP = 8,   // every kind and level count, group per pattern
+  FMX_HAS_KMER = 16,     // (no shape: the family's kernels can start from the k-mer table)
+};
+struct FmxRoute {
+  FmxShape shape;
+  int kind;              // FMX_KIND_*
+  int nl;                // wavelet levels, fixed at compile time for the common cases: 1, 2; 0 = any number
+  int sm;                // select structure the kernel is built for: 1 stored positions, 2 select blocks (endpoint per
+                         // lane); 0 hints + record search, valid for every vector (group per pattern); -1 not RLFM
+  bool km;               // the first kmer_k steps from the k-mer start table (u8 symbols)
+};
+static inline FmxRoute fmx_route(const fmx_index *idx, const FmxDev &dv, const FmxTune &tn, unsigned has) {
+  const FmxMwm &w = dv.bw;
+  const int sm = fmx_select_mode(idx, dv);
+  FmxRoute r;
+  r.kind = idx->kind;
+  r.nl = w.nlevels == 1 ? 1 : w.nlevels == 2 ? 2 : 0;
+  r.sm = idx->kind == FMX_KIND_RLFM ? 0 : -1;
+  r.km = (has & FMX_HAS_KMER) && dv.kmer != nullptr && tn.use_kmer && idx->sym_bytes == 1;
+  if ((has & FMX_SHAPE_PAIR) && dv.pair_rec && idx->sym_bytes == 1 && tn.use_pair && !tn.generic) {
+    r.shape = FMX_SHAPE_PAIR;
+  } else if (idx->kind == FMX_KIND_FM && idx->sym_bytes == 1 && w.nlevels == 1 && w.lv[0].fmt == 3 && !tn.generic) {
+    r.shape = FMX_SHAPE_F3;
+  } else if ((has & FMX_SHAPE_EP) && sm > 0 && !tn.generic) {
+    // RLFM whose B / B' have a one-load select (stored positions or select blocks -- every index the
+    // builder makes today): endpoint per lane (fmx_ep.h), 64 probes in flight per wave and stage.
+    // FM indexes keep the group-per-pattern kernels: their steps are one light record probe per level
+    // and those kernels already run at the request ceiling (endpoint per lane measured slower there:
+    // DNA 1.11 vs 0.67 ms, sigma = 255 two levels 0.97 vs 0.74 ms, benchmarks/gpu/ep_fm_count.sh)
+    r.shape = FMX_SHAPE_EP;
+    r.sm = sm;
+  } else {
+    r.shape = FMX_SHAPE_GROUP;                       // FM, multi-pieces, RLFM on hints + record search
+  }
+  return r;
+}
+// f(KIND, NL, SM, KM), every argument an integral constant: KIND and SM given, NL and KM from the route
+template <int V> using FmxInt = std::integral_constant<int, V>;
+template <int KIND, int SM, class F>
+static inline void fmx_route_nl_km(const FmxRoute &r, F f) {
+  auto nl = [&](auto km) {
+    if (r.nl == 1) f(FmxInt<KIND>{}, FmxInt<1>{}, FmxInt<SM>{}, km);
+    else if (r.nl == 2) f(FmxInt<KIND>{}, FmxInt<2>{}, FmxInt<SM>{}, km);
+    else f(FmxInt<KIND>{}, FmxInt<0>{}, FmxInt<SM>{}, km);
+  };
+  if (r.km) nl(std::true_type{}); else nl(std::false_type{});
+}
+// ... for the (KIND, SM) classes the ladder can select -- no other instantiation exists in the shipped library
+template <class F>
+static inline void fmx_route_ep(const FmxRoute &r, F f) {
+  if (r.sm == 1) fmx_route_nl_km<FMX_KIND_RLFM, 1>(r, f); else fmx_route_nl_km<FMX_KIND_RLFM, 2>(r, f);
+}
+template <class F>
+static inline void fmx_route_group(const FmxRoute &r, F f) {
+  if (r.kind == FMX_KIND_FM) fmx_route_nl_km<FMX_KIND_FM, -1>(r, f);
+  else if (r.kind == FMX_KIND_MULTI) fmx_route_nl_km<FMX_KIND_MULTI, -1>(r, f);
+  else fmx_route_nl_km<FMX_KIND_RLFM, 0>(r, f);
+}
+// f(KM) for the pair and one-level kernels
+template <class F>
+static inline void fmx_route_km(const FmxRoute &r, F f) {
+  if (r.km) f(std::true_type{}); else f(std::false_type{});
+}
+
+// ---- count: its kernels and argument lists (c = FmxCountCall; fmx_measure.inc launches them too) ----
 #define FMX_F3_LAUNCH(c, PPG, SKIP, KM)                                                              \
   hipLaunchKernelGGL((fmx_count_f3_kernel<PPG, SKIP, KM>),                                             \
                      dim3(fmx_grid_capped(((c).npat + PPG - 1) / PPG, (c).grid)), dim3(FMX_BLOCK), 0, (c).st, \
                      (c).dv.bw.lv[0].rec, (c).dv.n, (c).dv.max_character, (c).dv.status, (c).dv.kmer,  \
                      (c).dv.kmer_k, (c).dv.kmer_bits, (const uint8_t *)(c).pat, (c).off, (c).npat,     \
                      (c).s0e0, (c).s, (c).e, (c).cnt, (c).steps)
-#define FMX_PAIR_LAUNCH(c, KM)                                                                       \
-  hipLaunchKernelGGL(fmx_count_pair_kernel<KM>, dim3((c).grid), dim3(FMX_BLOCK), 0, (c).st,            \
-                     (c).dv.bw.lv[0].rec, (c).dv.pair_rec, (c).dv.n, (c).dv.max_character,             \
-                     (c).dv.pair_row0, (c).dv.pair_row1, (c).dv.status, (c).dv.kmer, (c).dv.kmer_k,    \
-                     (c).dv.kmer_bits, (const uint8_t *)(c).pat, (c).off, (c).npat, (c).s0e0, (c).s,   \
-                     (c).e, (c).cnt, (c).steps)
-// group per pattern; number of wavelet levels fixed at compile time for the common cases (1, 2)
-#define FMX_COUNT_LAUNCH(c, KIND, NL, SM)                                                            \
-  do {                                                                                               \
-    if ((c).km && (c).idx->sym_bytes == 1)                                                           \
-      hipLaunchKernelGGL((fmx_count_kernel<KIND, NL, true, SM>), dim3((c).grid), dim3(FMX_BLOCK), 0,   \
-                         (c).st, (c).dv, (c).pat, (c).off, (c).npat, (c).s0e0, (c).s, (c).e, (c).cnt,  \
-                         (c).steps);                                                                 \
-    else                                                                                             \
-      hipLaunchKernelGGL((fmx_count_kernel<KIND, NL, false, SM>), dim3((c).grid), dim3(FMX_BLOCK), 0,  \
-                         (c).st, (c).dv, (c).pat, (c).off, (c).npat, (c).s0e0, (c).s, (c).e, (c).cnt,  \
-                         (c).steps);                                                                 \
-  } while (0)
-#define FMX_COUNT_KIND(c, KIND, SM)                                                                  \
-  do {                                                                                               \
-    if ((c).dv.bw.nlevels == 1) FMX_COUNT_LAUNCH(c, KIND, 1, SM);                                    \
-    else if ((c).dv.bw.nlevels == 2) FMX_COUNT_LAUNCH(c, KIND, 2, SM);                               \
-    else FMX_COUNT_LAUNCH(c, KIND, 0, SM);                                                           \
-  } while (0)
-// endpoint per lane: one pattern per group while the grid lasts, `cap` blocks at most
-#define FMX_EP_LAUNCH(c, eb, KIND, NL, SM)                                                           \
-  do {                                                                                               \
-    if ((c).km && (c).idx->sym_bytes == 1)                                                           \
-      hipLaunchKernelGGL((fmx_count_ep_kernel<KIND, NL, SM, true>), dim3((unsigned)(eb)),              \
-                         dim3(FMX_BLOCK), 0, (c).st, (c).dv, (c).pat, (c).off, (c).npat, (c).s0e0,     \
-                         (c).s, (c).e, (c).cnt, (c).steps);                                          \
-    else                                                                                             \
-      hipLaunchKernelGGL((fmx_count_ep_kernel<KIND, NL, SM, false>), dim3((unsigned)(eb)),             \
-                         dim3(FMX_BLOCK), 0, (c).st, (c).dv, (c).pat, (c).off, (c).npat, (c).s0e0,     \
-                         (c).s, (c).e, (c).cnt, (c).steps);                                          \
-  } while (0)
-#define FMX_EP_SM(c, eb, KIND, SM)                                                                   \
-  do {                                                                                               \
-    if ((c).dv.bw.nlevels == 1) FMX_EP_LAUNCH(c, eb, KIND, 1, SM);                                   \
-    else if ((c).dv.bw.nlevels == 2) FMX_EP_LAUNCH(c, eb, KIND, 2, SM);                              \
-    else FMX_EP_LAUNCH(c, eb, KIND, 0, SM);                                                          \
-  } while (0)
+static inline auto fmx_count_pair(const FmxCountCall &c) {
+  return [&c](auto km) {
+    hipLaunchKernelGGL(fmx_count_pair_kernel<km()>, dim3(c.grid), dim3(FMX_BLOCK), 0, c.st, c.dv.bw.lv[0].rec,
+                       c.dv.pair_rec, c.dv.n, c.dv.max_character, c.dv.pair_row0, c.dv.pair_row1, c.dv.status,
+                       c.dv.kmer, c.dv.kmer_k, c.dv.kmer_bits, (const uint8_t *)c.pat, c.off, c.npat, c.s0e0, c.s,
+                       c.e, c.cnt, c.steps);
+  };
+}
+static inline auto fmx_count_group(const FmxCountCall &c) {
+  return [&c](auto kind, auto nl, auto sm, auto km) {
+    hipLaunchKernelGGL((fmx_count_kernel<kind(), nl(), km(), sm()>), dim3(c.grid), dim3(FMX_BLOCK), 0, c.st, c.dv,
+                       c.pat, c.off, c.npat, c.s0e0, c.s, c.e, c.cnt, c.steps);
+  };
+}
+// endpoint per lane: one pattern per group while the grid lasts, `eb` blocks at most
+static inline auto fmx_count_ep(const FmxCountCall &c, uint64_t eb) {
+  return [&c, eb](auto kind, auto nl, auto sm, auto km) {
+    hipLaunchKernelGGL((fmx_count_ep_kernel<kind(), nl(), sm(), km()>), dim3((unsigned)eb), dim3(FMX_BLOCK), 0, c.st,
+                       c.dv, c.pat, c.off, c.npat, c.s0e0, c.s, c.e, c.cnt, c.steps);
+  };
+}
 static inline uint64_t fmx_ep_count_blocks(uint64_t npat, long cap) {
   uint64_t eb = (npat + FMX_BLOCK / 8 - 1) / (FMX_BLOCK / 8);
   return eb > (uint64_t)cap ? (uint64_t)cap : eb;
@@ -2802,34 +2858,21 @@ int fmx_launch_count(const fmx_index *idx, const void *d_pat, const uint64_t *d_
   fmx_time_begin(idx, st);
   const FmxTune tn = fmx_tune();
   const FmxCountCall c{idx, dv, d_pat, d_off, npat, d_s0e0, d_s, d_e, d_cnt, idx->timing == 1 ? idx->d_steps : nullptr,
-                       st, dv.kmer != nullptr && tn.use_kmer, fmx_grid_capped(npat, max_blocks)};
-  const FmxMwm &w = dv.bw;
-  const int sm = fmx_select_mode(idx, dv);
+                       st, fmx_grid_capped(npat, max_blocks)};
+  const FmxRoute r = fmx_route(idx, dv, tn, FMX_SHAPE_PAIR | FMX_SHAPE_F3 | FMX_SHAPE_EP | FMX_SHAPE_GROUP | FMX_HAS_KMER);
   bool done = false;
 #ifdef FMX_MEASURE
-  done = fmx_measure_count(c, tn, sm);               // the alternative kernels, when one was asked for
+  done = fmx_measure_count(c, tn, r);                // the alternative kernels, when one was asked for
 #endif
   if (done) {
-  } else if (dv.pair_rec && idx->sym_bytes == 1 && tn.use_pair && !tn.generic) {
-    // opt-in pair index: two symbols per probe
-    if (c.km) FMX_PAIR_LAUNCH(c, true); else FMX_PAIR_LAUNCH(c, false);
-  } else if (idx->kind == FMX_KIND_FM && idx->sym_bytes == 1 && w.nlevels == 1 && w.lv[0].fmt == 3 && !tn.generic) {
-    // DNA (one 3-bit level): one 128-byte line per interval end and step, group per pattern
-    if (c.km) FMX_F3_LAUNCH(c, 1, false, true); else FMX_F3_LAUNCH(c, 1, false, false);
-  } else if (sm > 0 && !tn.generic) {
-    // RLFM whose B / B' have a one-load select (stored positions or select blocks -- every index the
-    // builder makes today): endpoint per lane (fmx_ep.h), 64 probes in flight per wave and stage.
-    // FM indexes keep the group-per-pattern kernels: their steps are one light record probe per level
-    // and those kernels already run at the request ceiling (endpoint per lane measured slower there:
-    // DNA 1.11 vs 0.67 ms, sigma = 255 two levels 0.97 vs 0.74 ms, benchmarks/gpu/ep_fm_count.sh)
-    const uint64_t eb = fmx_ep_count_blocks(npat, tn.ep_blocks);
-    if (sm == 1) FMX_EP_SM(c, eb, FMX_KIND_RLFM, 1); else FMX_EP_SM(c, eb, FMX_KIND_RLFM, 2);
-  } else if (idx->kind == FMX_KIND_FM) {
-    FMX_COUNT_KIND(c, FMX_KIND_FM, -1);
-  } else if (idx->kind == FMX_KIND_MULTI) {
-    FMX_COUNT_KIND(c, FMX_KIND_MULTI, -1);
+  } else if (r.shape == FMX_SHAPE_PAIR) {
+    fmx_route_km(r, fmx_count_pair(c));
+  } else if (r.shape == FMX_SHAPE_F3) {
+    if (r.km) FMX_F3_LAUNCH(c, 1, false, true); else FMX_F3_LAUNCH(c, 1, false, false);
+  } else if (r.shape == FMX_SHAPE_EP) {
+    fmx_route_ep(r, fmx_count_ep(c, fmx_ep_count_blocks(npat, tn.ep_blocks)));
   } else {
-    FMX_COUNT_KIND(c, FMX_KIND_RLFM, 0);             // hints + record search: valid for every vector
+    fmx_route_group(r, fmx_count_group(c));
   }
   fmx_time_end(idx, st);
   FMX_HIP(hipGetLastError());

@@ -13,8 +13,8 @@
 // pair probe that wide the state after two more.  An entry or probe below min_count says nothing about WHERE the match
 // stopped and the steps are taken one at a time.
 //
-// One kernel per count kernel of fmx_query.hip, same shapes (8-lane groups, one dwordx4 per lane and record, DPP sums,
-// the next symbol requested with the record loads, endpoint per lane for RLFM); the count kernels are left as they are.
+// One kernel per count kernel of fmx_query.hip and rung of its dispatch ladder (fmx_route), same shapes (8-lane groups,
+// one dwordx4 per lane and record, DPP sums, the next symbol with the record loads, endpoint per lane for RLFM).
 // `mc` is min_count clamped to 1 .. 2^32 - 1 by the launcher (n < 2^32 - 16: a larger value matches nothing either).
 #pragma once
 
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(FMX_BLOCK, 8) void fmx_sfx_kernel(
       const uint64_t pend = off[k + 1];
       j = (uint32_t)(pend - pbeg);
       // offsets that go backwards or leave the pattern buffer: refuse, do not read (j = 0 from here on)
-      bool bad = pend < pbeg || pbeg < pmin || pend > ptot || pend - pbeg > 0xFFFFFFFFull;
+      bool bad = FMX_SPAN_BAD32(pbeg, pend, pmin, ptot);
       s = 0; e = ix.n; len = 0;
       if (s0e0) {
         const uint64_t s64 = s0e0[2 * k], e64 = s0e0[2 * k + 1];
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(FMX_BLOCK) void fmx_sfx_empty_kernel(
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < npat; k += stride) {
     const uint64_t a = off[k], b = off[k + 1];
-    if (b < a || a < pmin || b > ptot || (s0e0 && (s0e0[2 * k] | s0e0[2 * k + 1]) != 0))
+    if (FMX_SPAN_BAD(a, b, pmin, ptot) || (s0e0 && (s0e0[2 * k] | s0e0[2 * k + 1]) != 0))
       atomicOr(status, 1u << FMX_ERR_ARG);
     if (out_s) out_s[k] = 0;
     if (out_e) out_e[k] = 0;
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(FMX_BLOCK) void fmx_sfx_f3_kernel(
       const uint64_t pend = off[k + 1];
       j = (uint32_t)(pend - pbeg);
       // offsets that go backwards or leave the pattern buffer: refuse, do not read (j = 0 from here on)
-      bool bad = pend < pbeg || pbeg < pmin || pend > ptot || pend - pbeg > 0xFFFFFFFFull;
+      bool bad = FMX_SPAN_BAD32(pbeg, pend, pmin, ptot);
       s = 0; e = n; len = 0;
       if (s0e0) {
         const uint64_t s64 = s0e0[2 * k], e64 = s0e0[2 * k + 1];
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(FMX_BLOCK) void fmx_sfx_pair_kernel(
       if (k + ngroups < npat) { nbeg = off[k + ngroups]; nend = off[k + ngroups + 1]; }
       j = (uint32_t)(pend - pbeg);
       // offsets that go backwards or leave the pattern buffer: refuse, do not read (j = 0 from here on)
-      bool bad = pend < pbeg || pbeg < pmin || pend > ptot || pend - pbeg > 0xFFFFFFFFull;
+      bool bad = FMX_SPAN_BAD32(pbeg, pend, pmin, ptot);
       s = 0; e = n; len = 0;
       if (s0e0) {
         const uint64_t s64 = s0e0[2 * k], e64 = s0e0[2 * k + 1];
@@ -333,7 +333,7 @@ __global__ __launch_bounds__(FMX_BLOCK) void fmx_sfx_ep_kernel(
       pbeg = off[k];
       const uint64_t pend = off[k + 1];
       j = (uint32_t)(pend - pbeg);
-      bool bad = pend < pbeg || pbeg < pmin || pend > ptot || pend - pbeg > 0xFFFFFFFFull;
+      bool bad = FMX_SPAN_BAD32(pbeg, pend, pmin, ptot);
       len = 0;
       uint32_t oth;                                      // the pair's other end
       if (s0e0) {
@@ -397,58 +397,7 @@ __global__ __launch_bounds__(FMX_BLOCK) void fmx_sfx_ep_kernel(
   }
 }
 
-// ---- launch ----
-struct FmxSfxCall {
-  const fmx_index *idx; FmxDev dv; const void *pat; const uint64_t *off; uint64_t npat; const uint64_t *s0e0;
-  uint32_t mc; uint64_t *s, *e, *cnt, *len; hipStream_t st; bool km; unsigned grid;
-};
-#define FMX_SFX_F3_LAUNCH(c, KM)                                                                     \
-  hipLaunchKernelGGL((fmx_sfx_f3_kernel<KM>), dim3((c).grid), dim3(FMX_BLOCK), 0, (c).st,              \
-                     (c).dv.bw.lv[0].rec, (c).dv.n, (c).dv.max_character, (c).dv.status, (c).dv.kmer,  \
-                     (c).dv.kmer_k, (c).dv.kmer_bits, (const uint8_t *)(c).pat, (c).off, (c).npat,     \
-                     (c).s0e0, (c).mc, (c).s, (c).e, (c).cnt, (c).len)
-#define FMX_SFX_PAIR_LAUNCH(c, KM)                                                                   \
-  hipLaunchKernelGGL(fmx_sfx_pair_kernel<KM>, dim3((c).grid), dim3(FMX_BLOCK), 0, (c).st,              \
-                     (c).dv.bw.lv[0].rec, (c).dv.pair_rec, (c).dv.n, (c).dv.max_character,             \
-                     (c).dv.pair_row0, (c).dv.pair_row1, (c).dv.status, (c).dv.kmer, (c).dv.kmer_k,    \
-                     (c).dv.kmer_bits, (const uint8_t *)(c).pat, (c).off, (c).npat, (c).s0e0, (c).mc,  \
-                     (c).s, (c).e, (c).cnt, (c).len)
-#define FMX_SFX_LAUNCH(c, KIND, NL, SM)                                                              \
-  do {                                                                                               \
-    if ((c).km && (c).idx->sym_bytes == 1)                                                           \
-      hipLaunchKernelGGL((fmx_sfx_kernel<KIND, NL, true, SM>), dim3((c).grid), dim3(FMX_BLOCK), 0,     \
-                         (c).st, (c).dv, (c).pat, (c).off, (c).npat, (c).s0e0, (c).mc, (c).s, (c).e,   \
-                         (c).cnt, (c).len);                                                          \
-    else                                                                                             \
-      hipLaunchKernelGGL((fmx_sfx_kernel<KIND, NL, false, SM>), dim3((c).grid), dim3(FMX_BLOCK), 0,    \
-                         (c).st, (c).dv, (c).pat, (c).off, (c).npat, (c).s0e0, (c).mc, (c).s, (c).e,   \
-                         (c).cnt, (c).len);                                                          \
-  } while (0)
-#define FMX_SFX_KIND(c, KIND, SM)                                                                    \
-  do {                                                                                               \
-    if ((c).dv.bw.nlevels == 1) FMX_SFX_LAUNCH(c, KIND, 1, SM);                                      \
-    else if ((c).dv.bw.nlevels == 2) FMX_SFX_LAUNCH(c, KIND, 2, SM);                                 \
-    else FMX_SFX_LAUNCH(c, KIND, 0, SM);                                                             \
-  } while (0)
-#define FMX_SFX_EP_LAUNCH(c, eb, KIND, NL, SM)                                                       \
-  do {                                                                                               \
-    if ((c).km && (c).idx->sym_bytes == 1)                                                           \
-      hipLaunchKernelGGL((fmx_sfx_ep_kernel<KIND, NL, SM, true>), dim3((unsigned)(eb)),                \
-                         dim3(FMX_BLOCK), 0, (c).st, (c).dv, (c).pat, (c).off, (c).npat, (c).s0e0,     \
-                         (c).mc, (c).s, (c).e, (c).cnt, (c).len);                                    \
-    else                                                                                             \
-      hipLaunchKernelGGL((fmx_sfx_ep_kernel<KIND, NL, SM, false>), dim3((unsigned)(eb)),               \
-                         dim3(FMX_BLOCK), 0, (c).st, (c).dv, (c).pat, (c).off, (c).npat, (c).s0e0,     \
-                         (c).mc, (c).s, (c).e, (c).cnt, (c).len);                                    \
-  } while (0)
-#define FMX_SFX_EP_SM(c, eb, KIND, SM)                                                               \
-  do {                                                                                               \
-    if ((c).dv.bw.nlevels == 1) FMX_SFX_EP_LAUNCH(c, eb, KIND, 1, SM);                               \
-    else if ((c).dv.bw.nlevels == 2) FMX_SFX_EP_LAUNCH(c, eb, KIND, 2, SM);                          \
-    else FMX_SFX_EP_LAUNCH(c, eb, KIND, 0, SM);                                                      \
-  } while (0)
-
-// the dispatch of fmx_launch_count, kernel for kernel
+// ---- launch: the ladder of fmx_route() (fmx_query.hip), every shape ----
 int fmx_launch_suffix_match(const fmx_index *idx, const void *d_pat, const uint64_t *d_off, uint64_t npat,
                             const uint64_t *d_s0e0, uint64_t min_count, uint64_t *d_s, uint64_t *d_e,
                             uint64_t *d_cnt, uint64_t *d_len, hipStream_t st) {
@@ -463,24 +412,32 @@ int fmx_launch_suffix_match(const fmx_index *idx, const void *d_pat, const uint6
     return FMX_OK;
   }
   const FmxTune tn = fmx_tune();
-  const FmxSfxCall c{idx, dv, d_pat, d_off, npat, d_s0e0,
-                     min_count > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)min_count, d_s, d_e, d_cnt, d_len,
-                     st, dv.kmer != nullptr && tn.use_kmer, fmx_grid_for_groups(npat)};
-  const FmxMwm &w = dv.bw;
-  const int sm = fmx_select_mode(idx, dv);
-  if (dv.pair_rec && idx->sym_bytes == 1 && tn.use_pair && !tn.generic) {
-    if (c.km) FMX_SFX_PAIR_LAUNCH(c, true); else FMX_SFX_PAIR_LAUNCH(c, false);
-  } else if (idx->kind == FMX_KIND_FM && idx->sym_bytes == 1 && w.nlevels == 1 && w.lv[0].fmt == 3 && !tn.generic) {
-    if (c.km) FMX_SFX_F3_LAUNCH(c, true); else FMX_SFX_F3_LAUNCH(c, false);
-  } else if (sm > 0 && !tn.generic) {
-    const uint64_t eb = fmx_ep_count_blocks(npat, tn.ep_blocks);
-    if (sm == 1) FMX_SFX_EP_SM(c, eb, FMX_KIND_RLFM, 1); else FMX_SFX_EP_SM(c, eb, FMX_KIND_RLFM, 2);
-  } else if (idx->kind == FMX_KIND_FM) {
-    FMX_SFX_KIND(c, FMX_KIND_FM, -1);
-  } else if (idx->kind == FMX_KIND_MULTI) {
-    FMX_SFX_KIND(c, FMX_KIND_MULTI, -1);
+  const FmxRoute r = fmx_route(idx, dv, tn, FMX_SHAPE_PAIR | FMX_SHAPE_F3 | FMX_SHAPE_EP | FMX_SHAPE_GROUP | FMX_HAS_KMER);
+  const uint32_t mc = min_count > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)min_count;
+  const dim3 grid(fmx_grid_for_groups(npat)), block(FMX_BLOCK);
+  const uint8_t *pat8 = (const uint8_t *)d_pat;
+  if (r.shape == FMX_SHAPE_PAIR) {
+    fmx_route_km(r, [&](auto km) {
+      hipLaunchKernelGGL(fmx_sfx_pair_kernel<km()>, grid, block, 0, st, dv.bw.lv[0].rec, dv.pair_rec, dv.n,
+                         dv.max_character, dv.pair_row0, dv.pair_row1, dv.status, dv.kmer, dv.kmer_k, dv.kmer_bits, pat8,
+                         d_off, npat, d_s0e0, mc, d_s, d_e, d_cnt, d_len);
+    });
+  } else if (r.shape == FMX_SHAPE_F3) {
+    fmx_route_km(r, [&](auto km) {
+      hipLaunchKernelGGL(fmx_sfx_f3_kernel<km()>, grid, block, 0, st, dv.bw.lv[0].rec, dv.n, dv.max_character, dv.status,
+                         dv.kmer, dv.kmer_k, dv.kmer_bits, pat8, d_off, npat, d_s0e0, mc, d_s, d_e, d_cnt, d_len);
+    });
+  } else if (r.shape == FMX_SHAPE_EP) {
+    const dim3 eb((unsigned)fmx_ep_count_blocks(npat, tn.ep_blocks));
+    fmx_route_ep(r, [&](auto kind, auto nl, auto sm, auto km) {
+      hipLaunchKernelGGL((fmx_sfx_ep_kernel<kind(), nl(), sm(), km()>), eb, block, 0, st, dv, d_pat, d_off, npat, d_s0e0,
+                         mc, d_s, d_e, d_cnt, d_len);
+    });
   } else {
-    FMX_SFX_KIND(c, FMX_KIND_RLFM, 0);               // hints + record search: valid for every vector
+    fmx_route_group(r, [&](auto kind, auto nl, auto sm, auto km) {
+      hipLaunchKernelGGL((fmx_sfx_kernel<kind(), nl(), km(), sm()>), grid, block, 0, st, dv, d_pat, d_off, npat, d_s0e0,
+                         mc, d_s, d_e, d_cnt, d_len);
+    });
   }
   FMX_HIP(hipGetLastError());
   return FMX_OK;

@@ -156,8 +156,7 @@ __global__ __launch_bounds__(FMXW_BLOCK) void fmxw_count_kernel(
   for (uint64_t k = gid; k < npat; k += ngroups) {
     const uint64_t pbeg = off[k], pend = off[k + 1];
     uint64_t j = pend - pbeg;
-    // offsets that go backwards or leave the pattern buffer: refuse, do not read
-    bool bad = pend < pbeg || pbeg < pmin || pend > ptot;
+    bool bad = FMX_SPAN_BAD(pbeg, pend, pmin, ptot);   // refuse, do not read
     uint64_t s = 0, e = w.n;                        // SearchIndexWrapper::search: (0, len)   wrapper.rs:41
     if (s0e0) {                                     // Search::search on an existing Search   wrapper.rs:105-106
       s = s0e0[2 * k];
@@ -246,8 +245,7 @@ __global__ __launch_bounds__(FMXW_BLOCK) void fmxw_count_pair_kernel(
   for (uint64_t k = gid; k < npat; k += ngroups) {
     const uint64_t pbeg = off[k], pend = off[k + 1];
     uint64_t j = pend - pbeg;
-    // offsets that go backwards or leave the pattern buffer: refuse, do not read
-    bool bad = pend < pbeg || pbeg < pmin || pend > ptot;
+    bool bad = FMX_SPAN_BAD(pbeg, pend, pmin, ptot);   // refuse, do not read
     uint64_t s = 0, e = w.n;                        // SearchIndexWrapper::search: (0, len)   wrapper.rs:41
     if (s0e0) {                                     // Search::search on an existing Search   wrapper.rs:105-106
       s = s0e0[2 * k];
@@ -1152,7 +1150,7 @@ __global__ __launch_bounds__(FMXW_BLOCK) void fmxw_g_count_kernel(
   for (uint64_t k = gid; k < npat; k += ngroups) {
     const uint64_t pbeg = off[k], pend = off[k + 1];
     uint64_t j = pend - pbeg;
-    bool bad = pend < pbeg || pbeg < pmin || pend > ptot;          // offsets that go backwards or leave the pattern buffer
+    bool bad = FMX_SPAN_BAD(pbeg, pend, pmin, ptot);
     uint64_t s = 0, e = w.n;                        // SearchIndexWrapper::search: (0, len)   wrapper.rs:41
     if (s0e0) {                                     // Search::search on an existing Search   wrapper.rs:105-106
       s = s0e0[2 * k];
@@ -1622,7 +1620,7 @@ __global__ __launch_bounds__(FMXW_BLOCK) void fmxw_g_count_ep_kernel(
       pbeg = off[k];
       const uint64_t pend = off[k + 1];
       j = pend - pbeg;
-      bool bad = pend < pbeg || pbeg < pmin || pend > ptot;          // offsets that go backwards or leave the pattern buffer
+      bool bad = FMX_SPAN_BAD(pbeg, pend, pmin, ptot);
       if (s0e0) {                                     // Search::search on an existing Search   wrapper.rs:105-106
         const uint64_t mine = s0e0[2 * k + is_e], other = s0e0[2 * k + (is_e ^ 1u)];
         pos = mine;

@@ -19,7 +19,7 @@ __global__ __launch_bounds__(FMXW_BLOCK) void fmxw_sfx_kernel(
     const uint64_t pbeg = off[k], pend = off[k + 1];
     uint64_t j = pend - pbeg, len = 0;
     // offsets that go backwards or leave the pattern buffer: refuse, do not read
-    bool bad = pend < pbeg || pbeg < pmin || pend > ptot;
+    bool bad = FMX_SPAN_BAD(pbeg, pend, pmin, ptot);
     uint64_t s = 0, e = w.n;
     if (s0e0) {
       s = s0e0[2 * k];
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(FMXW_BLOCK) void fmxw_sfx_pair_kernel(
     const uint64_t pbeg = off[k], pend = off[k + 1];
     uint64_t j = pend - pbeg, len = 0;
     // offsets that go backwards or leave the pattern buffer: refuse, do not read
-    bool bad = pend < pbeg || pbeg < pmin || pend > ptot;
+    bool bad = FMX_SPAN_BAD(pbeg, pend, pmin, ptot);
     uint64_t s = 0, e = w.n;
     if (s0e0) {
       s = s0e0[2 * k];
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(FMXW_BLOCK) void fmxw_g_sfx_kernel(
   for (uint64_t k = gid; k < npat; k += ngroups) {
     const uint64_t pbeg = off[k], pend = off[k + 1];
     uint64_t j = pend - pbeg, len = 0;
-    bool bad = pend < pbeg || pbeg < pmin || pend > ptot;          // offsets that go backwards or leave the pattern buffer
+    bool bad = FMX_SPAN_BAD(pbeg, pend, pmin, ptot);          // offsets that go backwards or leave the pattern buffer
     uint64_t s = 0, e = w.n;
     if (s0e0) {
       s = s0e0[2 * k];
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(FMXW_BLOCK) void fmxw_g_sfx_ep_kernel(
       const uint64_t pend = off[k + 1];
       j = pend - pbeg;
       len = 0;
-      bool bad = pend < pbeg || pbeg < pmin || pend > ptot;          // offsets that go backwards or leave the pattern buffer
+      bool bad = FMX_SPAN_BAD(pbeg, pend, pmin, ptot);          // offsets that go backwards or leave the pattern buffer
       uint64_t oth;                                   // the pair's other end
       if (s0e0) {
         const uint64_t mine = s0e0[2 * k + is_e], other = s0e0[2 * k + (is_e ^ 1u)];
