@@ -411,13 +411,19 @@ def test_partly_page_locked_array_takes_the_pageable_path():
     import ctypes as C
     import torch
     hip = C.CDLL(os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"))
+    page = 4096
+    probe = np.zeros(2 * page, dtype=np.uint8)                              # can this machine page-lock memory it already has?
+    at = probe.ctypes.data + (-probe.ctypes.data) % page
+    if hip.hipHostRegister(C.c_void_p(at), C.c_size_t(page), C.c_uint(0)) != 0:
+        hip.hipGetLastError()                                               # (or the next launch would report the refusal)
+        pytest.skip("hipHostRegister is not supported here")
+    assert hip.hipHostUnregister(C.c_void_p(at)) == 0
     t = W.dna_text_np(200000, 9)
     idx = F.FMIndex(F.Text.with_max_character(t, 4))
     lib = idx._lib
     npat = (1 << 17)
     flat, off, _ = W.substring_patterns_np(t, npat, 8, 3)
     want = idx.search_many(flat=flat, off=off)
-    page = 4096
     buf = np.zeros(len(flat) + 2 * page, dtype=np.uint8)
     start = (-buf.ctypes.data) % page                                      # a page-aligned window inside the buffer
     pat = buf[start:start + len(flat)]
