@@ -21,7 +21,7 @@ from . import _lib as L
 
 __all__ = ["Text", "Error", "FMIndex", "FMIndexWithLocate", "RLFMIndex", "RLFMIndexWithLocate",
            "FMIndexMultiPieces", "FMIndexMultiPiecesWithLocate", "Search", "Match", "SearchBatch",
-           "MismatchBatch", "MatchStatsBatch", "Replicas", "pack_patterns"]
+           "MismatchBatch", "MatchStatsBatch", "Replicas", "pack_patterns", "pack2"]
 
 
 class Error(Exception):
@@ -84,6 +84,28 @@ def pack_patterns(patterns, dtype=np.uint8):
         off[1:] = np.cumsum([len(p) for p in pats], dtype=np.uint64)
     flat = np.concatenate(pats) if pats and int(off[-1]) else np.zeros(1, dtype=dtype)
     return np.ascontiguousarray(flat, dtype=dtype), off
+
+
+def pack2(patterns=None, flat=None, off=None):
+    """symbols 1..4 -> the 2-bit packed stream of include/fmx.h: (words u64, off unchanged).  Symbol i of `flat` (numbered
+    like `off`) becomes the value symbol - 1 in bits [2 (i mod 32), 2 (i mod 32) + 2) of word i / 32; the symbols of
+    `flat` outside [off[0], off[-1]) are not looked at and their bits stay 0.  ValueError on a symbol outside 1..4."""
+    if flat is None:
+        flat, off = pack_patterns(patterns)
+    flat = np.asarray(flat)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    a, b = (int(off[0]), int(off[-1])) if len(off) else (0, 0)
+    if not 0 <= a <= b <= len(flat):
+        raise ValueError("offsets leave the symbols")
+    codes = flat[a:b].astype(np.int64) - 1
+    if codes.size and (codes.min() < 0 or codes.max() > 3):
+        raise ValueError("a 2-bit packed pattern holds symbols 1..4 only")
+    w0, nw = a // 32, max((b + 31) // 32 - a // 32, 1)
+    fields = np.zeros(nw * 32, dtype=np.uint64)
+    fields[a - 32 * w0:b - 32 * w0] = codes.astype(np.uint64)
+    words = np.zeros(w0 + nw, dtype=np.uint64)
+    words[w0:] = (fields.reshape(nw, 32) << (np.arange(32, dtype=np.uint64) * np.uint64(2))).sum(axis=1, dtype=np.uint64)
+    return words, off
 
 
 class Text:
@@ -211,6 +233,23 @@ class _Index:
         _check(self._lib.fmx_count_batch(self._h, _p(flat), _p(off), npat, _p(se), _p(s), _p(e),
                                          _p(c)))
         return SearchBatch(self, s[:npat], e[:npat], c[:npat])
+
+    def search_many_packed(self, words, off, s0e0=None):
+        """search_many on a 2-bit packed pattern stream (`pack2`; fmx_count_batch_packed2): the same SearchBatch.
+        One-level FM indexes over u8 symbols only (`packed2_supported()`); any other raises ERR_UNSUPPORTED."""
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        npat = len(off) - 1
+        if npat > 0 and int(off[-1]) > 32 * len(words):
+            raise Error(L.ERR_ARG, "off[-1] symbols do not fit %d words" % len(words))
+        s, e, c = (np.zeros(max(npat, 1), dtype=np.uint64) for _ in range(3))
+        se = None if s0e0 is None else np.ascontiguousarray(s0e0, dtype=np.uint64)
+        _check(self._lib.fmx_count_batch_packed2(self._h, _p(words), _p(off), npat, _p(se), _p(s), _p(e), _p(c)))
+        return SearchBatch(self, s[:npat], e[:npat], c[:npat])
+
+    def packed2_supported(self):
+        """does this index take 2-bit packed patterns (`search_many_packed`)?"""
+        return bool(self._lib.fmx_packed2_supported(self._h))
 
     def suffix_match_many(self, patterns=None, flat=None, off=None, s0e0=None, min_count=1):
         """longest suffix of every pattern whose interval keeps >= min_count rows (fmx_suffix_match_batch): a

@@ -377,6 +377,18 @@ int fmx_count_batch_dev(const fmx_index *idx, const void *d_pat, const uint64_t 
   return fmx_launch_count(idx, d_pat, d_pat_off, npat, d_s0e0, d_out_s, d_out_e,
                           d_out_count, (hipStream_t)stream);
 }
+int fmx_packed2_supported(const fmx_index *idx) {
+  return idx && idx->layout == FMX_LAYOUT && fmx_packed2_served(idx) ? 1 : 0;
+}
+int fmx_count_batch_packed2_dev(const fmx_index *idx, const uint64_t *d_pat_words, const uint64_t *d_pat_off,
+                                uint64_t npat, const uint64_t *d_s0e0, uint64_t *d_out_s, uint64_t *d_out_e,
+                                uint64_t *d_out_count, void *stream) {
+  CHECK_IDX(idx);
+  if (npat && (!d_pat_off)) return fail(FMX_ERR_ARG, "pat_off is NULL");
+  if ((uintptr_t)d_pat_words & 7u) return fail(FMX_ERR_ARG, "pat_words is not 8-byte aligned");
+  return fmx_launch_count_packed2(idx, d_pat_words, d_pat_off, npat, d_s0e0, d_out_s, d_out_e, d_out_count,
+                                  (hipStream_t)stream);
+}
 int fmx_suffix_match_batch_dev(const fmx_index *idx, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat,
                                const uint64_t *d_s0e0, uint64_t min_count, uint64_t *d_out_s, uint64_t *d_out_e,
                                uint64_t *d_out_count, uint64_t *d_out_len, void *stream) {
@@ -1097,6 +1109,80 @@ int fmx_count_resident_slice(const fmx_index *idx, const void *d_pat, const uint
   uint64_t *d_s = hc.take<uint64_t>(b_out), *d_e = hc.take<uint64_t>(b_out), *d_c = hc.take<uint64_t>(b_out);
   if (int rc = fmx_launch_count(idx, d_pat, d_pat_off, npat, d_s0e0, out_s ? d_s : nullptr, out_e ? d_e : nullptr,
                                 out_count ? d_c : nullptr, S)) {
+    (void)hipStreamSynchronize(S);
+    return rc;
+  }
+  if (out_s) FMX_HIP(hipMemcpyAsync(out_s, d_s, b_out, hipMemcpyDeviceToHost, S));
+  if (out_e) FMX_HIP(hipMemcpyAsync(out_e, d_e, b_out, hipMemcpyDeviceToHost, S));
+  if (out_count) FMX_HIP(hipMemcpyAsync(out_count, d_c, b_out, hipMemcpyDeviceToHost, S));
+  return finish_host_call(sx);
+}
+// fmx_count_batch on a 2-bit packed pattern stream (include/fmx.h): the words that hold symbols pat_off[0] ..
+// pat_off[npat] - 1 and the offsets go up, one launch, the results come down -- through the thread's small-call arena
+// when everything fits it, through the thread's retained scratch otherwise (no chunk pipeline: a 2^20 x 32 batch is
+// 8 MB of words).  The kernels keep the caller's absolute offsets: they get the address the device copy WOULD have if
+// it began at word 0 (never dereferenced below word pat_off[0] / 32: every pattern's offsets are checked).
+int fmx_count_batch_packed2(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off, uint64_t npat,
+                            const uint64_t *s0e0, uint64_t *out_s, uint64_t *out_e, uint64_t *out_count) {
+  CHECK_IDX(idx);
+  if (!fmx_packed2_served(idx))
+    return fail(FMX_ERR_UNSUPPORTED, "packed patterns need a one-level FM index over u8 symbols on the 32-bit engine");
+  if (npat == 0) return FMX_OK;
+  if (!pat_off) return fail(FMX_ERR_ARG, "pat_off is NULL");
+  const uint64_t total = pat_off[npat], first = pat_off[0];
+  if (first > total) return fail(FMX_ERR_ARG, "pat_off is not non-decreasing");
+  if (total > first && !pat_words) return fail(FMX_ERR_ARG, "pat_words is NULL");
+  const uint64_t w0 = first >> 5, nwords = total > first ? ((total - 1) >> 5) - w0 + 1 : 0;
+  const size_t b_words = (size_t)nwords * 8, b_out = (size_t)npat * 8, b_off = (size_t)(npat + 1) * 8;
+  if (b_words + npat * 48 + 128 <= kSmallUse) {
+    if (SmallCtx *sx = small_ctx(idx->device)) {
+      Arena a{sx};
+      const bool mapped = sx->hd != nullptr;
+      CallStatus cs(sx, mapped);
+      if (mapped) *status_host(sx) = 0; else FMX_HIP(hipMemsetAsync(status_dev(sx), 0, 4, sx->st));
+      const size_t ow = a.take(b_words ? b_words : 8), oo = a.take(b_off);
+      const size_t ose = a.take(s0e0 ? 2 * b_out : 0), in_end = a.off;
+      const size_t os = a.take(b_out), oe = a.take(b_out), oc = a.take(b_out), ost = a.off;
+      if (b_words) memcpy(a.host<uint8_t>(ow), pat_words + w0, b_words);
+      memcpy(a.host<uint8_t>(oo), pat_off, b_off);
+      if (s0e0) memcpy(a.host<uint8_t>(ose), s0e0, 2 * b_out);
+      FMX_HIP(hipMemcpyAsync(sx->d, sx->h, in_end, hipMemcpyHostToDevice, sx->st));
+      uint64_t *r_s = mapped ? a.mapped<uint64_t>(os) : a.dev<uint64_t>(os);
+      uint64_t *r_e = mapped ? a.mapped<uint64_t>(oe) : a.dev<uint64_t>(oe);
+      uint64_t *r_c = mapped ? a.mapped<uint64_t>(oc) : a.dev<uint64_t>(oc);
+      int rc = fmx_launch_count_packed2(idx, a.dev<uint64_t>(ow) - w0, a.dev<uint64_t>(oo), npat,
+                                        s0e0 ? a.dev<uint64_t>(ose) : nullptr, r_s, r_e, r_c, sx->st);
+      if (rc != FMX_OK) {
+        (void)hipStreamSynchronize(sx->st);
+        return rc;
+      }
+      if (mapped) {
+        rc = finish_mapped_call(sx);
+      } else {
+        FMX_HIP(hipMemcpyAsync(a.host<uint8_t>(os), a.dev<uint8_t>(os), (size_t)(ost - os), hipMemcpyDeviceToHost, sx->st));
+        rc = finish_host_call(sx);
+      }
+      if (out_s) memcpy(out_s, a.host<uint8_t>(os), b_out);
+      if (out_e) memcpy(out_e, a.host<uint8_t>(oe), b_out);
+      if (out_count) memcpy(out_count, a.host<uint8_t>(oc), b_out);
+      return rc;
+    }
+  }
+  HostCall hc;
+  FMX_HIP(hc.open(idx->device, HostCall::pad(b_words) + HostCall::pad(b_off) + (s0e0 ? HostCall::pad(2 * b_out) : 0) +
+                                   3 * HostCall::pad(b_out)));
+  uint64_t *d_words = hc.take<uint64_t>(b_words), *d_off = hc.take<uint64_t>(b_off);
+  uint64_t *d_se = s0e0 ? hc.take<uint64_t>(2 * b_out) : nullptr;
+  uint64_t *d_s = hc.take<uint64_t>(b_out), *d_e = hc.take<uint64_t>(b_out), *d_c = hc.take<uint64_t>(b_out);
+  SmallCtx *sx = hc.sx;
+  hipStream_t S = sx->st;
+  CallStatus cs(sx);
+  FMX_HIP(hipMemsetAsync(status_dev(sx), 0, 4, S));
+  if (b_words) FMX_HIP(hipMemcpyAsync(d_words, pat_words + w0, b_words, hipMemcpyHostToDevice, S));
+  FMX_HIP(hipMemcpyAsync(d_off, pat_off, b_off, hipMemcpyHostToDevice, S));
+  if (s0e0) FMX_HIP(hipMemcpyAsync(d_se, s0e0, 2 * b_out, hipMemcpyHostToDevice, S));
+  if (int rc = fmx_launch_count_packed2(idx, d_words - w0, d_off, npat, d_se, out_s ? d_s : nullptr,
+                                        out_e ? d_e : nullptr, out_count ? d_c : nullptr, S)) {
     (void)hipStreamSynchronize(S);
     return rc;
   }

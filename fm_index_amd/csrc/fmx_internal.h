@@ -385,6 +385,11 @@ static inline int fmx_keep(fmx_index *idx, void *p, uint64_t bytes) {
 int fmx_launch_count(const fmx_index *idx, const void *d_pat, const uint64_t *d_off,
                      uint64_t npat, const uint64_t *d_s0e0, uint64_t *d_s, uint64_t *d_e,
                      uint64_t *d_cnt, hipStream_t st, unsigned max_blocks = 0);
+// fmx_launch_count on a 2-bit packed pattern stream (fmx_packed.h; layout in include/fmx.h): one-level FM indexes over
+// u8 symbols on the 32-bit engine -- fmx_packed2_served() -- and FMX_ERR_UNSUPPORTED, nothing launched, for any other
+int fmx_launch_count_packed2(const fmx_index *idx, const uint64_t *d_words, const uint64_t *d_off, uint64_t npat,
+                             const uint64_t *d_s0e0, uint64_t *d_s, uint64_t *d_e, uint64_t *d_cnt, hipStream_t st);
+bool fmx_packed2_served(const fmx_index *idx);
 // longest suffix of every pattern whose interval keeps >= min_count rows (0 = 1): that interval and its length
 // (fmx_suffix.h / fmx_wide_suffix.h; any output may be NULL)
 int fmx_launch_suffix_match(const fmx_index *idx, const void *d_pat, const uint64_t *d_off, uint64_t npat,

@@ -258,6 +258,30 @@ int fmx_count_batch(const fmx_index *idx, const void *pat, const uint64_t *pat_o
 /* sticky device-side status of *_dev calls on this handle; reading clears it */
 int fmx_stream_status(const fmx_index *idx);
 
+/* ---- the same count on 2-bit packed DNA patterns ---------------------------- */
+/* The form DNA reads are usually held in, and a quarter of the bytes on the host link.  A packed pattern buffer is an
+ * array of little-endian uint64_t words: symbol number i lives in bits [2 (i mod 32), 2 (i mod 32) + 2) of word
+ * i / 32, where i uses the same absolute numbering as pat_off, and the stored value is symbol - 1 -- symbols 1..4 can
+ * be expressed, symbol 0 cannot.  Pattern k is symbols [pat_off[k], pat_off[k+1]); patterns may start and end
+ * anywhere inside a word, and a slice of a larger batch keeps its absolute offsets.  The call reads only words
+ * pat_off[0] / 32 .. (pat_off[npat] - 1) / 32; the bits of those words outside [pat_off[0], pat_off[npat]) are read
+ * but influence no result, and no word outside that range is touched, whatever the offsets say.
+ * Outputs and status are those of fmx_count_batch / fmx_count_batch_dev on the unpacked byte patterns: the (s, e)
+ * pair left by the early exit, `s0e0` refinement, FMX_ERR_ARG for bad offsets or an `s0e0` entry above len() (such a
+ * pattern is never read, its outputs are 0), FMX_ERR_SYMBOL_RANGE when a code with code + 1 > max_character is
+ * reached (that pattern's outputs are 0).  An empty text is served like there.
+ * Served: FMX_KIND_FM over u8 symbols with one 3-bit wavelet level (max_character <= 7) on the 32-bit engine, with or
+ * without the pair index and the k-mer start table -- fmx_packed2_supported() returns 1.  Any other handle (the
+ * 64-bit engine, run-length, multi-pieces, larger alphabets) gets FMX_ERR_UNSUPPORTED and nothing is written.
+ * The dev form needs d_pat_words 8-byte aligned (FMX_ERR_ARG before any launch otherwise); it only launches kernels on
+ * `stream` -- no allocation, no synchronisation, capturable -- and reports through fmx_stream_status(). */
+int fmx_count_batch_packed2_dev(const fmx_index *idx, const uint64_t *d_pat_words, const uint64_t *d_pat_off,
+                                uint64_t npat, const uint64_t *d_s0e0, uint64_t *d_out_s, uint64_t *d_out_e,
+                                uint64_t *d_out_count, void *stream);
+int fmx_count_batch_packed2(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off, uint64_t npat,
+                            const uint64_t *s0e0, uint64_t *out_s, uint64_t *out_e, uint64_t *out_count);
+int fmx_packed2_supported(const fmx_index *idx);   /* 1: this index takes the two calls above */
+
 /* ---- longest suffix of a pattern that occurs: its interval and its length ---- */
 /* An ADDITION with no counterpart in the crate; the closest is Search::search (wrapper.rs:99-124) repeated one
  * symbol at a time until count() falls below min_count.  For pattern k = pat[pat_off[k] .. pat_off[k+1]) and
