@@ -251,6 +251,23 @@ class _Index:
         """does this index take 2-bit packed patterns (`search_many_packed`)?"""
         return bool(self._lib.fmx_packed2_supported(self._h))
 
+    def search_many_packed_both_strands(self, words, off):
+        """both strands of every pattern of a 2-bit packed stream in one call (fmx_count_batch_packed2_rc): a
+        SearchBatch of 2 * npat entries, entry 2k pattern k as written, entry 2k + 1 its reverse complement
+        (reversed, symbol c -> 5 - c).  `packed2_rc_supported()` indexes only; any other raises ERR_UNSUPPORTED."""
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        npat = len(off) - 1
+        if npat > 0 and int(off[-1]) > 32 * len(words):
+            raise Error(L.ERR_ARG, "off[-1] symbols do not fit %d words" % len(words))
+        s, e, c = (np.zeros(max(2 * npat, 1), dtype=np.uint64) for _ in range(3))
+        _check(self._lib.fmx_count_batch_packed2_rc(self._h, _p(words), _p(off), npat, _p(s), _p(e), _p(c)))
+        return SearchBatch(self, s[:2 * npat], e[:2 * npat], c[:2 * npat])
+
+    def packed2_rc_supported(self):
+        """does this index take `search_many_packed_both_strands` (packed patterns, max_character >= 4)?"""
+        return bool(self._lib.fmx_packed2_rc_supported(self._h))
+
     def suffix_match_many(self, patterns=None, flat=None, off=None, s0e0=None, min_count=1):
         """longest suffix of every pattern whose interval keeps >= min_count rows (fmx_suffix_match_batch): a
         SearchBatch of that interval with `.lengths` (numpy u64), so `.locate()` gives the seed positions.  A symbol

@@ -389,6 +389,18 @@ int fmx_count_batch_packed2_dev(const fmx_index *idx, const uint64_t *d_pat_word
   return fmx_launch_count_packed2(idx, d_pat_words, d_pat_off, npat, d_s0e0, d_out_s, d_out_e, d_out_count,
                                   (hipStream_t)stream);
 }
+int fmx_packed2_rc_supported(const fmx_index *idx) {
+  return idx && idx->layout == FMX_LAYOUT && fmx_packed2_rc_served(idx) ? 1 : 0;
+}
+int fmx_count_batch_packed2_rc_dev(const fmx_index *idx, const uint64_t *d_pat_words, const uint64_t *d_pat_off,
+                                   uint64_t npat, uint64_t *d_out_s, uint64_t *d_out_e, uint64_t *d_out_count,
+                                   void *stream) {
+  CHECK_IDX(idx);
+  if (npat && (!d_pat_off)) return fail(FMX_ERR_ARG, "pat_off is NULL");
+  if ((uintptr_t)d_pat_words & 7u) return fail(FMX_ERR_ARG, "pat_words is not 8-byte aligned");
+  return fmx_launch_count_packed2_rc(idx, d_pat_words, d_pat_off, npat, d_out_s, d_out_e, d_out_count,
+                                     (hipStream_t)stream);
+}
 int fmx_suffix_match_batch_dev(const fmx_index *idx, const void *d_pat, const uint64_t *d_pat_off, uint64_t npat,
                                const uint64_t *d_s0e0, uint64_t min_count, uint64_t *d_out_s, uint64_t *d_out_e,
                                uint64_t *d_out_count, uint64_t *d_out_len, void *stream) {
@@ -1122,36 +1134,44 @@ int fmx_count_resident_slice(const fmx_index *idx, const void *d_pat, const uint
 // when everything fits it, through the thread's retained scratch otherwise (no chunk pipeline: a 2^20 x 32 batch is
 // 8 MB of words).  The kernels keep the caller's absolute offsets: they get the address the device copy WOULD have if
 // it began at word 0 (never dereferenced below word pat_off[0] / 32: every pattern's offsets are checked).
-int fmx_count_batch_packed2(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off, uint64_t npat,
-                            const uint64_t *s0e0, uint64_t *out_s, uint64_t *out_e, uint64_t *out_count) {
+// `both`: fmx_count_batch_packed2_rc -- the same words and offsets, uploaded once; 2 npat results come down (no s0e0).
+static int count_packed2_host(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off, uint64_t npat,
+                              const uint64_t *s0e0, uint64_t *out_s, uint64_t *out_e, uint64_t *out_count, bool both) {
   CHECK_IDX(idx);
-  if (!fmx_packed2_served(idx))
-    return fail(FMX_ERR_UNSUPPORTED, "packed patterns need a one-level FM index over u8 symbols on the 32-bit engine");
+  if (both ? !fmx_packed2_rc_served(idx) : !fmx_packed2_served(idx))
+    return fail(FMX_ERR_UNSUPPORTED, both ? "both-strand packed patterns need a packed-pattern index with max_character >= 4"
+                                          : "packed patterns need a one-level FM index over u8 symbols on the 32-bit engine");
   if (npat == 0) return FMX_OK;
   if (!pat_off) return fail(FMX_ERR_ARG, "pat_off is NULL");
   const uint64_t total = pat_off[npat], first = pat_off[0];
   if (first > total) return fail(FMX_ERR_ARG, "pat_off is not non-decreasing");
   if (total > first && !pat_words) return fail(FMX_ERR_ARG, "pat_words is NULL");
   const uint64_t w0 = first >> 5, nwords = total > first ? ((total - 1) >> 5) - w0 + 1 : 0;
-  const size_t b_words = (size_t)nwords * 8, b_out = (size_t)npat * 8, b_off = (size_t)(npat + 1) * 8;
-  if (b_words + npat * 48 + 128 <= kSmallUse) {
+  const size_t b_words = (size_t)nwords * 8, b_out = (size_t)npat * (both ? 16 : 8), b_off = (size_t)(npat + 1) * 8,
+               b_se = s0e0 ? (size_t)npat * 16 : 0;
+  auto launch = [&](const uint64_t *dw, const uint64_t *dof, const uint64_t *dse, uint64_t *ds, uint64_t *de,
+                    uint64_t *dc, hipStream_t st) {
+    return both ? fmx_launch_count_packed2_rc(idx, dw, dof, npat, ds, de, dc, st)
+                : fmx_launch_count_packed2(idx, dw, dof, npat, dse, ds, de, dc, st);
+  };
+  if (b_words + npat * (both ? 56 : 48) + 128 <= kSmallUse) {
     if (SmallCtx *sx = small_ctx(idx->device)) {
       Arena a{sx};
       const bool mapped = sx->hd != nullptr;
       CallStatus cs(sx, mapped);
       if (mapped) *status_host(sx) = 0; else FMX_HIP(hipMemsetAsync(status_dev(sx), 0, 4, sx->st));
       const size_t ow = a.take(b_words ? b_words : 8), oo = a.take(b_off);
-      const size_t ose = a.take(s0e0 ? 2 * b_out : 0), in_end = a.off;
+      const size_t ose = a.take(b_se), in_end = a.off;
       const size_t os = a.take(b_out), oe = a.take(b_out), oc = a.take(b_out), ost = a.off;
       if (b_words) memcpy(a.host<uint8_t>(ow), pat_words + w0, b_words);
       memcpy(a.host<uint8_t>(oo), pat_off, b_off);
-      if (s0e0) memcpy(a.host<uint8_t>(ose), s0e0, 2 * b_out);
+      if (s0e0) memcpy(a.host<uint8_t>(ose), s0e0, b_se);
       FMX_HIP(hipMemcpyAsync(sx->d, sx->h, in_end, hipMemcpyHostToDevice, sx->st));
       uint64_t *r_s = mapped ? a.mapped<uint64_t>(os) : a.dev<uint64_t>(os);
       uint64_t *r_e = mapped ? a.mapped<uint64_t>(oe) : a.dev<uint64_t>(oe);
       uint64_t *r_c = mapped ? a.mapped<uint64_t>(oc) : a.dev<uint64_t>(oc);
-      int rc = fmx_launch_count_packed2(idx, a.dev<uint64_t>(ow) - w0, a.dev<uint64_t>(oo), npat,
-                                        s0e0 ? a.dev<uint64_t>(ose) : nullptr, r_s, r_e, r_c, sx->st);
+      int rc = launch(a.dev<uint64_t>(ow) - w0, a.dev<uint64_t>(oo), s0e0 ? a.dev<uint64_t>(ose) : nullptr, r_s, r_e, r_c,
+                      sx->st);
       if (rc != FMX_OK) {
         (void)hipStreamSynchronize(sx->st);
         return rc;
@@ -1169,10 +1189,10 @@ int fmx_count_batch_packed2(const fmx_index *idx, const uint64_t *pat_words, con
     }
   }
   HostCall hc;
-  FMX_HIP(hc.open(idx->device, HostCall::pad(b_words) + HostCall::pad(b_off) + (s0e0 ? HostCall::pad(2 * b_out) : 0) +
+  FMX_HIP(hc.open(idx->device, HostCall::pad(b_words) + HostCall::pad(b_off) + (s0e0 ? HostCall::pad(b_se) : 0) +
                                    3 * HostCall::pad(b_out)));
   uint64_t *d_words = hc.take<uint64_t>(b_words), *d_off = hc.take<uint64_t>(b_off);
-  uint64_t *d_se = s0e0 ? hc.take<uint64_t>(2 * b_out) : nullptr;
+  uint64_t *d_se = s0e0 ? hc.take<uint64_t>(b_se) : nullptr;
   uint64_t *d_s = hc.take<uint64_t>(b_out), *d_e = hc.take<uint64_t>(b_out), *d_c = hc.take<uint64_t>(b_out);
   SmallCtx *sx = hc.sx;
   hipStream_t S = sx->st;
@@ -1180,9 +1200,9 @@ int fmx_count_batch_packed2(const fmx_index *idx, const uint64_t *pat_words, con
   FMX_HIP(hipMemsetAsync(status_dev(sx), 0, 4, S));
   if (b_words) FMX_HIP(hipMemcpyAsync(d_words, pat_words + w0, b_words, hipMemcpyHostToDevice, S));
   FMX_HIP(hipMemcpyAsync(d_off, pat_off, b_off, hipMemcpyHostToDevice, S));
-  if (s0e0) FMX_HIP(hipMemcpyAsync(d_se, s0e0, 2 * b_out, hipMemcpyHostToDevice, S));
-  if (int rc = fmx_launch_count_packed2(idx, d_words - w0, d_off, npat, d_se, out_s ? d_s : nullptr,
-                                        out_e ? d_e : nullptr, out_count ? d_c : nullptr, S)) {
+  if (s0e0) FMX_HIP(hipMemcpyAsync(d_se, s0e0, b_se, hipMemcpyHostToDevice, S));
+  if (int rc = launch(d_words - w0, d_off, d_se, out_s ? d_s : nullptr, out_e ? d_e : nullptr,
+                      out_count ? d_c : nullptr, S)) {
     (void)hipStreamSynchronize(S);
     return rc;
   }
@@ -1190,6 +1210,14 @@ int fmx_count_batch_packed2(const fmx_index *idx, const uint64_t *pat_words, con
   if (out_e) FMX_HIP(hipMemcpyAsync(out_e, d_e, b_out, hipMemcpyDeviceToHost, S));
   if (out_count) FMX_HIP(hipMemcpyAsync(out_count, d_c, b_out, hipMemcpyDeviceToHost, S));
   return finish_host_call(sx);
+}
+int fmx_count_batch_packed2(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off, uint64_t npat,
+                            const uint64_t *s0e0, uint64_t *out_s, uint64_t *out_e, uint64_t *out_count) {
+  return count_packed2_host(idx, pat_words, pat_off, npat, s0e0, out_s, out_e, out_count, false);
+}
+int fmx_count_batch_packed2_rc(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off, uint64_t npat,
+                               uint64_t *out_s, uint64_t *out_e, uint64_t *out_count) {
+  return count_packed2_host(idx, pat_words, pat_off, npat, nullptr, out_s, out_e, out_count, true);
 }
 // Host arrays in, host arrays out: upload, one launch, download, on the calling thread's stream (none of the chunk
 // pipelines of fmx_count_batch).  Like fmx_count_batch the call moves pat[pat_off[0] .. pat_off[npat]) only and the

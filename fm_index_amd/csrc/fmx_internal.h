@@ -390,6 +390,11 @@ int fmx_launch_count(const fmx_index *idx, const void *d_pat, const uint64_t *d_
 int fmx_launch_count_packed2(const fmx_index *idx, const uint64_t *d_words, const uint64_t *d_off, uint64_t npat,
                              const uint64_t *d_s0e0, uint64_t *d_s, uint64_t *d_e, uint64_t *d_cnt, hipStream_t st);
 bool fmx_packed2_served(const fmx_index *idx);
+// both strands of every packed pattern in one launch (fmx_packed_rc.h): outputs of 2 npat entries, slot 2k the pattern,
+// slot 2k + 1 its reverse complement; fmx_packed2_rc_served(): fmx_packed2_served() and max_character >= 4
+int fmx_launch_count_packed2_rc(const fmx_index *idx, const uint64_t *d_words, const uint64_t *d_off, uint64_t npat,
+                                uint64_t *d_s, uint64_t *d_e, uint64_t *d_cnt, hipStream_t st);
+bool fmx_packed2_rc_served(const fmx_index *idx);
 // longest suffix of every pattern whose interval keeps >= min_count rows (0 = 1): that interval and its length
 // (fmx_suffix.h / fmx_wide_suffix.h; any output may be NULL)
 int fmx_launch_suffix_match(const fmx_index *idx, const void *d_pat, const uint64_t *d_off, uint64_t npat,

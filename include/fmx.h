@@ -282,6 +282,30 @@ int fmx_count_batch_packed2(const fmx_index *idx, const uint64_t *pat_words, con
                             const uint64_t *s0e0, uint64_t *out_s, uint64_t *out_e, uint64_t *out_count);
 int fmx_packed2_supported(const fmx_index *idx);   /* 1: this index takes the two calls above */
 
+/* ---- both strands of every packed pattern in one call ------------------------ */
+/* A read is searched on both strands.  Inputs are those of fmx_count_batch_packed2* -- the same word layout, absolute
+ * offsets, only words pat_off[0] / 32 .. (pat_off[npat] - 1) / 32 are read and their other bits influence nothing, an
+ * 8-byte aligned d_pat_words (FMX_ERR_ARG before any launch otherwise) -- without `s0e0`: prepending to an existing
+ * search has no meaning for the other strand.  The output arrays have 2 * npat entries (any of them may be NULL):
+ *   slot 2k      pattern k as written: what fmx_count_batch_packed2 gives on the same input;
+ *   slot 2k + 1  its reverse complement R, R[t] = 5 - P[m - 1 - t] (symbols paired (1, 4) and (2, 3); stored code x
+ *                <-> x ^ 3): what fmx_count_batch gives on the bytes of R from (0, len), the (s, e) pair left by the
+ *                early exit included.  R is formed in registers; the words cross the host link once.
+ * The arrays feed fmx_offsets_dev and fmx_locate_batch* unchanged, with npat = 2 * npat.  Bad offsets are FMX_ERR_ARG
+ * as in the packed call: the pattern is never read and both its slots hold 0.  An empty pattern gives (0, len) in
+ * both slots; an empty text (0, 0) everywhere, the offsets still checked.
+ * Served: every index fmx_packed2_supported() accepts whose max_character is at least 4 -- every complemented code is a
+ * symbol of the index, so there is no FMX_ERR_SYMBOL_RANGE case; fmx_packed2_rc_supported() returns 1.  Alphabets of 2
+ * or 3 symbols and every handle the packed call refuses get FMX_ERR_UNSUPPORTED and nothing is written.
+ * The dev form only launches kernels on `stream` -- no allocation, no synchronisation, capturable -- and reports
+ * through fmx_stream_status(); the host form uploads the words and offsets once and launches once. */
+int fmx_count_batch_packed2_rc_dev(const fmx_index *idx, const uint64_t *d_pat_words, const uint64_t *d_pat_off,
+                                   uint64_t npat, uint64_t *d_out_s, uint64_t *d_out_e, uint64_t *d_out_count,
+                                   void *stream);
+int fmx_count_batch_packed2_rc(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off, uint64_t npat,
+                               uint64_t *out_s, uint64_t *out_e, uint64_t *out_count);
+int fmx_packed2_rc_supported(const fmx_index *idx);   /* 1: this index takes the two calls above */
+
 /* ---- longest suffix of a pattern that occurs: its interval and its length ---- */
 /* An ADDITION with no counterpart in the crate; the closest is Search::search (wrapper.rs:99-124) repeated one
  * symbol at a time until count() falls below min_count.  For pattern k = pat[pat_off[k] .. pat_off[k+1]) and
