@@ -314,6 +314,35 @@ class _Index:
         return MatchStatsBatch(self, off - off[0] if npat > 0 else np.zeros(1, dtype=np.uint64), ln[:total],
                                s[:total], e[:total])
 
+    def match_stats_many_packed(self, words, off, min_count=1, max_len=0, min_seed_len=0):
+        """match_stats_many on a 2-bit packed pattern stream (`pack2`; fmx_match_stats_batch_packed2): the same
+        MatchStatsBatch.  `packed2_supported()` indexes only; any other raises ERR_UNSUPPORTED."""
+        return self._match_stats_packed(words, off, min_count, max_len, min_seed_len, 1)
+
+    def match_stats_many_packed_both_strands(self, words, off, min_count=1, max_len=0, min_seed_len=0):
+        """both strands of every pattern of a 2-bit packed stream in one call (fmx_match_stats_batch_packed2_rc): a
+        MatchStatsBatch over 2 * npat patterns, entry 2k pattern k as written, entry 2k + 1 its reverse complement
+        (reversed, symbol c -> 5 - c), so `begin` of a seed of an odd entry counts in the reverse complement.
+        `packed2_rc_supported()` indexes only; any other raises ERR_UNSUPPORTED."""
+        return self._match_stats_packed(words, off, min_count, max_len, min_seed_len, 2)
+
+    def _match_stats_packed(self, words, off, min_count, max_len, min_seed_len, strands):
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        npat = len(off) - 1
+        if npat > 0 and int(off[-1]) > 32 * len(words):
+            raise Error(L.ERR_ARG, "off[-1] symbols do not fit %d words" % len(words))
+        total = int(off[-1] - off[0]) if npat > 0 and off[-1] >= off[0] else 0
+        s, e, ln = (np.zeros(max(strands * total, 1), dtype=np.uint64) for _ in range(3))
+        call = self._lib.fmx_match_stats_batch_packed2_rc if strands == 2 else self._lib.fmx_match_stats_batch_packed2
+        _check(call(self._h, _p(words), _p(off), npat, int(min_count), int(max_len), int(min_seed_len), _p(s), _p(e),
+                    _p(ln)))
+        voff = off - off[0] if npat > 0 else np.zeros(1, dtype=np.uint64)
+        if strands == 2 and npat > 0:                               # the virtual batch: P_0, R_0, P_1, R_1, ...
+            voff = np.append(np.stack([voff[:-1] * np.uint64(2), voff[:-1] + voff[1:]], axis=1).reshape(-1),
+                             voff[-1] * np.uint64(2))
+        return MatchStatsBatch(self, voff, ln[:strands * total], s[:strands * total], e[:strands * total])
+
     def locate_many(self, s, e):
         """(offsets u64[npat+1], positions u64[total]) in the reference's iteration order."""
         s = np.ascontiguousarray(s, dtype=np.uint64)

@@ -456,6 +456,44 @@ int fmx_match_stats_batch_dev(const fmx_index *idx, const void *d_pat, const uin
   return fmx_launch_match_stats(idx, d_pat, d_pat_off, npat, total_syms, min_count, max_len, min_seed_len, d_out_s,
                                 d_out_e, d_out_len, (hipStream_t)stream);
 }
+// the packed forms: the handle is checked first (nothing is written for one the route does not serve), then the
+// arguments; npat == 0 as in the byte call, over the slots of every strand
+static int match_stats_packed2_dev(const fmx_index *idx, const uint64_t *d_pat_words, const uint64_t *d_pat_off,
+                                   uint64_t npat, uint64_t total_syms, uint64_t min_count, uint64_t max_len,
+                                   uint64_t min_seed_len, uint64_t *d_out_s, uint64_t *d_out_e, uint64_t *d_out_len,
+                                   bool both, void *stream) {
+  CHECK_IDX(idx);
+  if (both ? !fmx_packed2_rc_served(idx) : !fmx_packed2_served(idx))
+    return fail(FMX_ERR_UNSUPPORTED, both ? "both-strand packed patterns need a packed-pattern index with max_character >= 4"
+                                          : "packed patterns need a one-level FM index over u8 symbols on the 32-bit engine");
+  if (!d_out_len) return fail(FMX_ERR_ARG, "out_len is NULL");
+  if ((uintptr_t)d_pat_words & 7u) return fail(FMX_ERR_ARG, "pat_words is not 8-byte aligned");
+  if (npat == 0) {                                   // no pattern owns a slot: all of them are empty
+    if (total_syms == 0) return FMX_OK;
+    const size_t b = (size_t)total_syms * (both ? 16 : 8);
+    if (d_out_s) FMX_HIP(hipMemsetAsync(d_out_s, 0, b, (hipStream_t)stream));
+    if (d_out_e) FMX_HIP(hipMemsetAsync(d_out_e, 0, b, (hipStream_t)stream));
+    FMX_HIP(hipMemsetAsync(d_out_len, 0, b, (hipStream_t)stream));
+    return fail(FMX_ERR_ARG, "total_syms is not pat_off[npat] - pat_off[0]");
+  }
+  if (!d_pat_off) return fail(FMX_ERR_ARG, "pat_off is NULL");
+  return fmx_launch_match_stats_packed2(idx, d_pat_words, d_pat_off, npat, total_syms, min_count, max_len, min_seed_len,
+                                        d_out_s, d_out_e, d_out_len, both, (hipStream_t)stream);
+}
+int fmx_match_stats_batch_packed2_dev(const fmx_index *idx, const uint64_t *d_pat_words, const uint64_t *d_pat_off,
+                                      uint64_t npat, uint64_t total_syms, uint64_t min_count, uint64_t max_len,
+                                      uint64_t min_seed_len, uint64_t *d_out_s, uint64_t *d_out_e, uint64_t *d_out_len,
+                                      void *stream) {
+  return match_stats_packed2_dev(idx, d_pat_words, d_pat_off, npat, total_syms, min_count, max_len, min_seed_len,
+                                 d_out_s, d_out_e, d_out_len, false, stream);
+}
+int fmx_match_stats_batch_packed2_rc_dev(const fmx_index *idx, const uint64_t *d_pat_words, const uint64_t *d_pat_off,
+                                         uint64_t npat, uint64_t total_syms, uint64_t min_count, uint64_t max_len,
+                                         uint64_t min_seed_len, uint64_t *d_out_s, uint64_t *d_out_e,
+                                         uint64_t *d_out_len, void *stream) {
+  return match_stats_packed2_dev(idx, d_pat_words, d_pat_off, npat, total_syms, min_count, max_len, min_seed_len,
+                                 d_out_s, d_out_e, d_out_len, true, stream);
+}
 int fmx_offsets_dev(const fmx_index *idx, const uint64_t *d_s, const uint64_t *d_e, uint64_t npat,
                     uint64_t *d_out_off, void *stream) {
   CHECK_IDX(idx);
@@ -1386,6 +1424,59 @@ int fmx_match_stats_batch(const fmx_index *idx, const void *pat, const uint64_t 
   if (out_e && b_out) FMX_HIP(hipMemcpyAsync(out_e, d_e, b_out, hipMemcpyDeviceToHost, S));
   if (b_out) FMX_HIP(hipMemcpyAsync(out_len, d_l, b_out, hipMemcpyDeviceToHost, S));
   return finish_host_call(sx);
+}
+// The matching statistics of a 2-bit packed pattern stream on host arrays: the staging of count_packed2_host (the
+// words that hold symbols pat_off[0] .. pat_off[npat] - 1 and the offsets go up once, the kernels get the address the
+// device copy would have if it began at word 0), the kernels of fmx_packed_mstats.h, three arrays of one entry per
+// pattern symbol -- per strand with `both` -- come down.  No chunk pipeline.
+static int match_stats_packed2_host(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off,
+                                    uint64_t npat, uint64_t min_count, uint64_t max_len, uint64_t min_seed_len,
+                                    uint64_t *out_s, uint64_t *out_e, uint64_t *out_len, bool both) {
+  CHECK_IDX(idx);
+  if (both ? !fmx_packed2_rc_served(idx) : !fmx_packed2_served(idx))
+    return fail(FMX_ERR_UNSUPPORTED, both ? "both-strand packed patterns need a packed-pattern index with max_character >= 4"
+                                          : "packed patterns need a one-level FM index over u8 symbols on the 32-bit engine");
+  if (!out_len) return fail(FMX_ERR_ARG, "out_len is NULL");
+  if (npat == 0) return FMX_OK;
+  if (!pat_off) return fail(FMX_ERR_ARG, "pat_off is NULL");
+  const uint64_t total = pat_off[npat], first = pat_off[0];
+  if (first > total) return fail(FMX_ERR_ARG, "pat_off is not non-decreasing");
+  const uint64_t span = total - first;
+  if (span && !pat_words) return fail(FMX_ERR_ARG, "pat_words is NULL");
+  const uint64_t w0 = first >> 5, nwords = span ? ((total - 1) >> 5) - w0 + 1 : 0;
+  const size_t b_words = (size_t)nwords * 8, b_out = (size_t)span * (both ? 16 : 8), b_off = (size_t)(npat + 1) * 8;
+  HostCall hc;
+  FMX_HIP(hc.open(idx->device, HostCall::pad(b_words) + HostCall::pad(b_off) + 3 * (HostCall::pad(b_out) + 256)));
+  uint64_t *d_words = hc.take<uint64_t>(b_words), *d_off = hc.take<uint64_t>(b_off);
+  uint64_t *d_s = hc.take<uint64_t>(b_out), *d_e = hc.take<uint64_t>(b_out), *d_l = hc.take<uint64_t>(b_out);
+  SmallCtx *sx = hc.sx;
+  hipStream_t S = sx->st;
+  CallStatus cs(sx);
+  FMX_HIP(hipMemsetAsync(status_dev(sx), 0, 4, S));
+  if (b_words) FMX_HIP(hipMemcpyAsync(d_words, pat_words + w0, b_words, hipMemcpyHostToDevice, S));
+  FMX_HIP(hipMemcpyAsync(d_off, pat_off, b_off, hipMemcpyHostToDevice, S));
+  // (virtual: word 0 of the caller's buffer -- never dereferenced below word `w0`)
+  if (int rc = fmx_launch_match_stats_packed2(idx, d_words - w0, d_off, npat, span, min_count, max_len, min_seed_len,
+                                              out_s ? d_s : nullptr, out_e ? d_e : nullptr, d_l, both, S)) {
+    (void)hipStreamSynchronize(S);
+    return rc;
+  }
+  if (out_s && b_out) FMX_HIP(hipMemcpyAsync(out_s, d_s, b_out, hipMemcpyDeviceToHost, S));
+  if (out_e && b_out) FMX_HIP(hipMemcpyAsync(out_e, d_e, b_out, hipMemcpyDeviceToHost, S));
+  if (b_out) FMX_HIP(hipMemcpyAsync(out_len, d_l, b_out, hipMemcpyDeviceToHost, S));
+  return finish_host_call(sx);
+}
+int fmx_match_stats_batch_packed2(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off,
+                                  uint64_t npat, uint64_t min_count, uint64_t max_len, uint64_t min_seed_len,
+                                  uint64_t *out_s, uint64_t *out_e, uint64_t *out_len) {
+  return match_stats_packed2_host(idx, pat_words, pat_off, npat, min_count, max_len, min_seed_len, out_s, out_e,
+                                  out_len, false);
+}
+int fmx_match_stats_batch_packed2_rc(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off,
+                                     uint64_t npat, uint64_t min_count, uint64_t max_len, uint64_t min_seed_len,
+                                     uint64_t *out_s, uint64_t *out_e, uint64_t *out_len) {
+  return match_stats_packed2_host(idx, pat_words, pat_off, npat, min_count, max_len, min_seed_len, out_s, out_e,
+                                  out_len, true);
 }
 void fmx_set_error_text(const char *text) { g_last_error = text ? text : ""; }
 

@@ -415,6 +415,12 @@ int fmx_launch_mismatch(const fmx_index *idx, const void *d_pat, const uint64_t 
 int fmx_launch_match_stats(const fmx_index *idx, const void *d_pat, const uint64_t *d_off, uint64_t npat,
                            uint64_t total, uint64_t min_count, uint64_t max_len, uint64_t min_seed_len,
                            uint64_t *d_s, uint64_t *d_e, uint64_t *d_len, hipStream_t st);
+// fmx_launch_match_stats on a 2-bit packed pattern stream (fmx_packed_mstats.h), for the handles fmx_packed2_served()
+// accepts; both = true: the virtual batch of both strands, arrays of 2 total entries, for fmx_packed2_rc_served()
+// handles.  The caller has checked the handle.  `total` is the span of the offsets either way.  npat > 0.
+int fmx_launch_match_stats_packed2(const fmx_index *idx, const uint64_t *d_words, const uint64_t *d_off, uint64_t npat,
+                                   uint64_t total, uint64_t min_count, uint64_t max_len, uint64_t min_seed_len,
+                                   uint64_t *d_s, uint64_t *d_e, uint64_t *d_len, bool both, hipStream_t st);
 // rows_ws / tile_ws: caller-provided scratch (fmx_locate_rows_bytes / fmx_offsets_tile_bytes); NULL = take
 // it from the stream-ordered allocator for the duration of the call
 int fmx_launch_locate(const fmx_index *idx, const uint64_t *d_s, const uint64_t *d_e,

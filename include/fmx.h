@@ -440,6 +440,42 @@ int fmx_match_stats_batch(const fmx_index *idx, const void *pat, const uint64_t 
                           uint64_t min_count, uint64_t max_len, uint64_t min_seed_len,
                           uint64_t *out_s, uint64_t *out_e, uint64_t *out_len);
 
+/* ---- the same on 2-bit packed DNA patterns, one strand or both --------------- */
+/* fmx_match_stats_batch* for the pattern form of fmx_count_batch_packed2*: the same word layout and absolute offsets,
+ * only words pat_off[0] / 32 .. (pat_off[npat] - 1) / 32 are read and their other bits influence nothing, d_pat_words
+ * 8-byte aligned (FMX_ERR_ARG before any launch otherwise).  total_syms is pat_off[npat] - pat_off[0].
+ *
+ * fmx_match_stats_batch_packed2*: outputs and status are bit-identical to fmx_match_stats_batch* on the unpacked
+ * bytes (symbol = code + 1): the slot numbering t = pat_off[k] - pat_off[0] + i - 1, min_count, max_len, the seed
+ * filter, (0, 0) where L == 0, FMX_ERR_ARG for out_len == NULL, bad offsets (the slots of such a pattern hold 0) and a
+ * total_syms that is not the span of the offsets; nothing outside [0, total_syms) is written.  A code whose symbol is
+ * above max_character ends the match and is no error.  Served: what fmx_packed2_supported() accepts.
+ *
+ * fmx_match_stats_batch_packed2_rc*: both strands from the same words.  The results are those of the byte call on the
+ * virtual batch of 2 npat patterns V[2k] = P_k, V[2k + 1] = R_k, R[t] = 5 - P[m - 1 - t], with the offsets voff[2k] =
+ * 2 (pat_off[k] - pat_off[0]) and voff[2k + 1] = voff[2k] + m_k: the three arrays have 2 * total_syms entries, every
+ * virtual pattern is a pattern to the seed filter (its last slot is a pattern end), bad offsets zero the slots of both
+ * strands of that pattern, and the even virtual patterns are what the single-strand call gives.  R is formed in
+ * registers; the words and offsets cross the host link once.  Served: what fmx_packed2_rc_supported() accepts.
+ *
+ * Every other handle gets FMX_ERR_UNSUPPORTED and nothing is written.  There is no `s0e0`, as in the byte call.  The
+ * dev forms allocate nothing and never synchronise (kernels and hipMemsetAsync on `stream` only), can be captured and
+ * report through fmx_stream_status(); the host forms upload once, run the same kernels and synchronise. */
+int fmx_match_stats_batch_packed2_dev(const fmx_index *idx, const uint64_t *d_pat_words, const uint64_t *d_pat_off,
+                                      uint64_t npat, uint64_t total_syms, uint64_t min_count, uint64_t max_len,
+                                      uint64_t min_seed_len, uint64_t *d_out_s, uint64_t *d_out_e, uint64_t *d_out_len,
+                                      void *stream);
+int fmx_match_stats_batch_packed2(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off,
+                                  uint64_t npat, uint64_t min_count, uint64_t max_len, uint64_t min_seed_len,
+                                  uint64_t *out_s, uint64_t *out_e, uint64_t *out_len);
+int fmx_match_stats_batch_packed2_rc_dev(const fmx_index *idx, const uint64_t *d_pat_words, const uint64_t *d_pat_off,
+                                         uint64_t npat, uint64_t total_syms, uint64_t min_count, uint64_t max_len,
+                                         uint64_t min_seed_len, uint64_t *d_out_s, uint64_t *d_out_e,
+                                         uint64_t *d_out_len, void *stream);
+int fmx_match_stats_batch_packed2_rc(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off,
+                                     uint64_t npat, uint64_t min_count, uint64_t max_len, uint64_t min_seed_len,
+                                     uint64_t *out_s, uint64_t *out_e, uint64_t *out_len);
+
 /* ---- Search::iter_matches().map(MatchWithLocate::locate) ------------------ */
 /* (wrapper.rs:137-139, 203-217, 238-242 -> fm_index.rs:127-140, sample.rs:46-60)
  *     out_pos[out_off[k] + j] = get_sa(s[k] + j),  j = 0 .. e[k]-s[k]-1
