@@ -296,6 +296,33 @@ class _Index:
                                                    _p(ooff), total, _p(s), _p(e), _p(ed)))
         return MismatchBatch(self, cnt[:npat], nint[:npat], ooff, s[:total], e[:total], ed[:2 * total])
 
+    def mismatch_hits_many_packed(self, words, off, max_mismatches=1, max_hits=8):
+        """the first `max_hits` intervals of every pattern of a 2-bit packed stream (`pack2`) within `max_mismatches`
+        (0, 1 or 2) substitutions, in the order of mismatch_search_many, in ONE pass
+        (fmx_mismatch_hits_batch_packed2): a MismatchHits.  `packed2_supported()` indexes only."""
+        return self._mismatch_hits_packed(words, off, max_mismatches, max_hits, 1)
+
+    def mismatch_hits_many_packed_both_strands(self, words, off, max_mismatches=1, max_hits=8):
+        """the same on both strands from one upload (fmx_mismatch_hits_batch_packed2_rc): a MismatchHits over 2 * npat
+        entries, entry 2k pattern k as written, entry 2k + 1 its reverse complement (reversed, symbol c -> 5 - c; edit
+        positions of an odd entry count in the reverse complement).  `packed2_rc_supported()` indexes only."""
+        return self._mismatch_hits_packed(words, off, max_mismatches, max_hits, 2)
+
+    def _mismatch_hits_packed(self, words, off, max_mismatches, max_hits, strands):
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        npat, mh = len(off) - 1, int(max_hits)
+        if npat > 0 and int(off[-1]) > 32 * len(words):
+            raise Error(L.ERR_ARG, "off[-1] symbols do not fit %d words" % len(words))
+        nv = strands * npat
+        nint, cnt = (np.zeros(max(nv, 1), dtype=np.uint64) for _ in range(2))
+        s, e = (np.zeros(max(nv * mh, 1), dtype=np.uint64) for _ in range(2))
+        ed = np.full(2 * max(nv * mh, 1), 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)
+        call = self._lib.fmx_mismatch_hits_batch_packed2_rc if strands == 2 else self._lib.fmx_mismatch_hits_batch_packed2
+        _check(call(self._h, _p(words), _p(off), npat, int(max_mismatches), mh, _p(nint), _p(cnt), _p(s), _p(e), _p(ed)))
+        return MismatchHits(self, nint[:nv], cnt[:nv], s[:nv * mh].reshape(nv, mh), e[:nv * mh].reshape(nv, mh),
+                            ed[:2 * nv * mh].reshape(nv, mh, 2))
+
     def match_stats_many(self, patterns=None, flat=None, off=None, min_count=1, max_len=0, min_seed_len=0):
         """backward matching statistics of every pattern (fmx_match_stats_batch): for every end position the longest
         suffix of that prefix whose interval keeps >= min_count rows (at most max_len symbols, 0 = no cap), one entry
@@ -729,6 +756,31 @@ class MismatchBatch:
     def locate(self):
         """(offsets u64[total + 1], positions u64[hits]): the positions of every interval (fmx_locate_batch)"""
         return self._ix.locate_many(self.s, self.e)
+
+
+class MismatchHits:
+    """Result of mismatch_hits_many_packed*: `max_hits` slots per (virtual) pattern.  `nint`, `counts` (nv,): the exact
+    number of intervals and of occurrences, also where they did not fit; `s`, `e` (nv, max_hits): the first intervals,
+    (0, 0) in unused slots; `edits`: masked (nv, max_hits, 2) array of MismatchBatch's (pos, sym) records; `truncated`
+    (nv,): more intervals exist than slots."""
+
+    def __init__(self, index, nint, counts, s, e, edit_words):
+        self._ix = index
+        self.nint = nint
+        self.counts = counts
+        self.s = s
+        self.e = e
+        self.truncated = nint > np.uint64(s.shape[1])
+        rec = np.zeros(edit_words.shape, dtype=[("pos", np.uint64), ("sym", np.uint64)])
+        unused = edit_words == np.uint64(0xFFFFFFFFFFFFFFFF)
+        rec["pos"] = np.where(unused, 0, edit_words >> np.uint64(32))
+        rec["sym"] = np.where(unused, 0, edit_words & np.uint64(0xFFFFFFFF))
+        self.edits = np.ma.masked_array(rec, mask=unused)
+
+    def locate(self):
+        """(offsets u64[nv * max_hits + 1], positions u64[hits]): the positions of every slot, slot v * max_hits + j
+        interval j of entry v; an unused slot has none (fmx_locate_batch)"""
+        return self._ix.locate_many(self.s.reshape(-1), self.e.reshape(-1))
 
 
 class MatchStatsBatch:

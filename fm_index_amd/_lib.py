@@ -85,6 +85,10 @@ SYMBOLS = [
     ("fmx_mismatch_count_batch", _I, [_V, _V, _V, _U64, _V, _U32, _V, _V]),
     ("fmx_mismatch_search_batch_dev", _I, [_V, _V, _V, _U64, _V, _U32, _V, _U64, _V, _V, _V, _V]),
     ("fmx_mismatch_search_batch", _I, [_V, _V, _V, _U64, _V, _U32, _V, _U64, _V, _V, _V]),
+    ("fmx_mismatch_hits_batch_packed2_dev", _I, [_V, _V, _V, _U64, _U32, _U64, _V, _V, _V, _V, _V, _V]),
+    ("fmx_mismatch_hits_batch_packed2", _I, [_V, _V, _V, _U64, _U32, _U64, _V, _V, _V, _V, _V]),
+    ("fmx_mismatch_hits_batch_packed2_rc_dev", _I, [_V, _V, _V, _U64, _U32, _U64, _V, _V, _V, _V, _V, _V]),
+    ("fmx_mismatch_hits_batch_packed2_rc", _I, [_V, _V, _V, _U64, _U32, _U64, _V, _V, _V, _V, _V]),
     ("fmx_match_stats_batch_dev", _I, [_V, _V, _V, _U64, _U64, _U64, _U64, _U64, _V, _V, _V, _V]),
     ("fmx_match_stats_batch", _I, [_V, _V, _V, _U64, _U64, _U64, _U64, _V, _V, _V]),
     ("fmx_match_stats_batch_packed2_dev", _I, [_V, _V, _V, _U64, _U64, _U64, _U64, _U64, _V, _V, _V, _V]),

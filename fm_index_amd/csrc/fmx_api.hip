@@ -434,8 +434,45 @@ int fmx_mismatch_search_batch_dev(const fmx_index *idx, const void *d_pat, const
   return fmx_launch_mismatch(idx, d_pat, d_pat_off, npat, d_s0e0, max_mismatches, true, d_out_off, total_intervals,
                              nullptr, nullptr, d_out_s, d_out_e, d_out_edit, (hipStream_t)stream);
 }
+// what both forms of the packed one-pass mismatch search refuse before anything is launched: the handle first (nothing
+// is written for one the route does not serve), then the budget and a slot count that does not fit 64 bits
+#define CHECK_MISMATCH_HITS_P2(idx, npat, max_mismatches, max_hits, both)                                           \
+  if ((both) ? !fmx_packed2_rc_served(idx) : !fmx_packed2_served(idx))                                              \
+    return fail(FMX_ERR_UNSUPPORTED, (both) ? "both-strand packed patterns need a packed-pattern index with max_character >= 4" \
+                                            : "packed patterns need a one-level FM index over u8 symbols on the 32-bit engine"); \
+  if ((max_mismatches) > FMX_MAX_MISMATCHES) return fail(FMX_ERR_ARG, "max_mismatches exceeds FMX_MAX_MISMATCHES"); \
+  uint64_t _slots = 0;                                                                                              \
+  if (__builtin_mul_overflow((uint64_t)(npat), (uint64_t)((both) ? 4 : 2), &_slots) ||                              \
+      __builtin_mul_overflow(_slots, (uint64_t)(max_hits), &_slots))                                                \
+    return fail(FMX_ERR_ARG, "2 * nv * max_hits does not fit 64 bits")
+static int mismatch_hits_packed2_dev(const fmx_index *idx, const uint64_t *d_pat_words, const uint64_t *d_pat_off,
+                                     uint64_t npat, uint32_t max_mismatches, uint64_t max_hits, uint64_t *d_out_nint,
+                                     uint64_t *d_out_count, uint64_t *d_out_s, uint64_t *d_out_e, uint64_t *d_out_edit,
+                                     bool both, void *stream) {
+  CHECK_IDX(idx);
+  CHECK_MISMATCH_HITS_P2(idx, npat, max_mismatches, max_hits, both);
+  if ((uintptr_t)d_pat_words & 7u) return fail(FMX_ERR_ARG, "pat_words is not 8-byte aligned");
+  if (npat == 0) return FMX_OK;
+  if (!d_pat_off) return fail(FMX_ERR_ARG, "pat_off is NULL");
+  return fmx_launch_mismatch_hits_packed2(idx, d_pat_words, d_pat_off, npat, max_mismatches, max_hits, d_out_nint,
+                                          d_out_count, d_out_s, d_out_e, d_out_edit, both, (hipStream_t)stream);
+}
+int fmx_mismatch_hits_batch_packed2_dev(const fmx_index *idx, const uint64_t *d_pat_words, const uint64_t *d_pat_off,
+                                        uint64_t npat, uint32_t max_mismatches, uint64_t max_hits, uint64_t *d_out_nint,
+                                        uint64_t *d_out_count, uint64_t *d_out_s, uint64_t *d_out_e,
+                                        uint64_t *d_out_edit, void *stream) {
+  return mismatch_hits_packed2_dev(idx, d_pat_words, d_pat_off, npat, max_mismatches, max_hits, d_out_nint, d_out_count,
+                                   d_out_s, d_out_e, d_out_edit, false, stream);
+}
+int fmx_mismatch_hits_batch_packed2_rc_dev(const fmx_index *idx, const uint64_t *d_pat_words, const uint64_t *d_pat_off,
+                                           uint64_t npat, uint32_t max_mismatches, uint64_t max_hits,
+                                           uint64_t *d_out_nint, uint64_t *d_out_count, uint64_t *d_out_s,
+                                           uint64_t *d_out_e, uint64_t *d_out_edit, void *stream) {
+  return mismatch_hits_packed2_dev(idx, d_pat_words, d_pat_off, npat, max_mismatches, max_hits, d_out_nint, d_out_count,
+                                   d_out_s, d_out_e, d_out_edit, true, stream);
+}
 // what both forms of the matching statistics refuse before anything is launched
-#define CHECK_MATCH_STATS(idx, out_len)                                                                  \
+#define CHECK_MATCH_STATS(idx, out_len)                                                                 \
   if ((idx)->is_wide)                                                                                    \
     return fail(FMX_ERR_UNSUPPORTED, "the matching statistics are not available on the 64-bit engine (n >= 2^32 - 16 or FMX_FLAG_FORCE_WIDE)"); \
   if (!(out_len)) return fail(FMX_ERR_ARG, "out_len is NULL")
@@ -1477,6 +1514,64 @@ int fmx_match_stats_batch_packed2_rc(const fmx_index *idx, const uint64_t *pat_w
                                      uint64_t *out_s, uint64_t *out_e, uint64_t *out_len) {
   return match_stats_packed2_host(idx, pat_words, pat_off, npat, min_count, max_len, min_seed_len, out_s, out_e,
                                   out_len, true);
+}
+// The packed one-pass mismatch search on host arrays: the staging of match_stats_packed2_host (the words that hold
+// symbols pat_off[0] .. pat_off[npat] - 1 and the offsets go up once, the kernel gets the address the device copy would
+// have if it began at word 0), one launch, and the arrays the caller asked for come down: nv totals, nv * max_hits
+// slots.  Every slot is written by the call, so nothing is uploaded for them.  No chunk pipeline.
+static int mismatch_hits_packed2_host(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off,
+                                      uint64_t npat, uint32_t max_mismatches, uint64_t max_hits, uint64_t *out_nint,
+                                      uint64_t *out_count, uint64_t *out_s, uint64_t *out_e, uint64_t *out_edit,
+                                      bool both) {
+  CHECK_IDX(idx);
+  CHECK_MISMATCH_HITS_P2(idx, npat, max_mismatches, max_hits, both);
+  if (_slots > (SIZE_MAX >> 5)) return fail(FMX_ERR_ARG, "nv * max_hits slots do not fit the address space");
+  if (npat == 0) return FMX_OK;
+  if (!pat_off) return fail(FMX_ERR_ARG, "pat_off is NULL");
+  const uint64_t total = pat_off[npat], first = pat_off[0];
+  if (first > total) return fail(FMX_ERR_ARG, "pat_off is not non-decreasing");
+  if (total > first && !pat_words) return fail(FMX_ERR_ARG, "pat_words is NULL");
+  const uint64_t w0 = first >> 5, nwords = total > first ? ((total - 1) >> 5) - w0 + 1 : 0;
+  const size_t b_words = (size_t)nwords * 8, b_off = (size_t)(npat + 1) * 8, b_pp = (size_t)npat * (both ? 16 : 8),
+               b_slot = (size_t)_slots * 4;                       // one of out_s / out_e; out_edit is twice that
+  HostCall hc;
+  FMX_HIP(hc.open(idx->device, HostCall::pad(b_words) + HostCall::pad(b_off) + 2 * HostCall::pad(b_pp) +
+                                   4 * HostCall::pad(b_slot) + 4 * 256));   // (an empty array still takes a line)
+  uint64_t *d_words = hc.take<uint64_t>(b_words), *d_off = hc.take<uint64_t>(b_off);
+  uint64_t *d_n = hc.take<uint64_t>(b_pp), *d_c = hc.take<uint64_t>(b_pp);
+  uint64_t *d_s = hc.take<uint64_t>(b_slot), *d_e = hc.take<uint64_t>(b_slot), *d_ed = hc.take<uint64_t>(2 * b_slot);
+  SmallCtx *sx = hc.sx;
+  hipStream_t S = sx->st;
+  CallStatus cs(sx);
+  FMX_HIP(hipMemsetAsync(status_dev(sx), 0, 4, S));
+  if (b_words) FMX_HIP(hipMemcpyAsync(d_words, pat_words + w0, b_words, hipMemcpyHostToDevice, S));
+  FMX_HIP(hipMemcpyAsync(d_off, pat_off, b_off, hipMemcpyHostToDevice, S));
+  // (virtual: word 0 of the caller's buffer -- never dereferenced below word `w0`)
+  if (int rc = fmx_launch_mismatch_hits_packed2(idx, d_words - w0, d_off, npat, max_mismatches, max_hits,
+                                                out_nint ? d_n : nullptr, out_count ? d_c : nullptr,
+                                                out_s ? d_s : nullptr, out_e ? d_e : nullptr,
+                                                out_edit ? d_ed : nullptr, both, S)) {
+    (void)hipStreamSynchronize(S);
+    return rc;
+  }
+  if (out_nint) FMX_HIP(hipMemcpyAsync(out_nint, d_n, b_pp, hipMemcpyDeviceToHost, S));
+  if (out_count) FMX_HIP(hipMemcpyAsync(out_count, d_c, b_pp, hipMemcpyDeviceToHost, S));
+  if (out_s && b_slot) FMX_HIP(hipMemcpyAsync(out_s, d_s, b_slot, hipMemcpyDeviceToHost, S));
+  if (out_e && b_slot) FMX_HIP(hipMemcpyAsync(out_e, d_e, b_slot, hipMemcpyDeviceToHost, S));
+  if (out_edit && b_slot) FMX_HIP(hipMemcpyAsync(out_edit, d_ed, 2 * b_slot, hipMemcpyDeviceToHost, S));
+  return finish_host_call(sx);
+}
+int fmx_mismatch_hits_batch_packed2(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off,
+                                    uint64_t npat, uint32_t max_mismatches, uint64_t max_hits, uint64_t *out_nint,
+                                    uint64_t *out_count, uint64_t *out_s, uint64_t *out_e, uint64_t *out_edit) {
+  return mismatch_hits_packed2_host(idx, pat_words, pat_off, npat, max_mismatches, max_hits, out_nint, out_count, out_s,
+                                    out_e, out_edit, false);
+}
+int fmx_mismatch_hits_batch_packed2_rc(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off,
+                                       uint64_t npat, uint32_t max_mismatches, uint64_t max_hits, uint64_t *out_nint,
+                                       uint64_t *out_count, uint64_t *out_s, uint64_t *out_e, uint64_t *out_edit) {
+  return mismatch_hits_packed2_host(idx, pat_words, pat_off, npat, max_mismatches, max_hits, out_nint, out_count, out_s,
+                                    out_e, out_edit, true);
 }
 void fmx_set_error_text(const char *text) { g_last_error = text ? text : ""; }
 

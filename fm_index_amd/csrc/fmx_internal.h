@@ -421,6 +421,13 @@ int fmx_launch_match_stats(const fmx_index *idx, const void *d_pat, const uint64
 int fmx_launch_match_stats_packed2(const fmx_index *idx, const uint64_t *d_words, const uint64_t *d_off, uint64_t npat,
                                    uint64_t total, uint64_t min_count, uint64_t max_len, uint64_t min_seed_len,
                                    uint64_t *d_s, uint64_t *d_e, uint64_t *d_len, bool both, hipStream_t st);
+// the mismatch search on a 2-bit packed pattern stream in one pass (fmx_packed_mismatch.h): virtual pattern v (k, or
+// 2 k + strand with both = true) gets d_nint[v] / d_cnt[v] and its first max_hits intervals in slots v * max_hits ..
+// of d_s / d_e / d_edit (2 entries per slot), the unused ones filled.  The caller has checked the handle
+// (fmx_packed2_served / fmx_packed2_rc_served), max_mismatches and that 2 * nv * max_hits fits 64 bits.  npat > 0.
+int fmx_launch_mismatch_hits_packed2(const fmx_index *idx, const uint64_t *d_words, const uint64_t *d_off, uint64_t npat,
+                                     uint32_t max_mismatches, uint64_t max_hits, uint64_t *d_nint, uint64_t *d_cnt,
+                                     uint64_t *d_s, uint64_t *d_e, uint64_t *d_edit, bool both, hipStream_t st);
 // rows_ws / tile_ws: caller-provided scratch (fmx_locate_rows_bytes / fmx_offsets_tile_bytes); NULL = take
 // it from the stream-ordered allocator for the duration of the call
 int fmx_launch_locate(const fmx_index *idx, const uint64_t *d_s, const uint64_t *d_e,

@@ -392,6 +392,51 @@ int fmx_mismatch_search_batch(const fmx_index *idx, const void *pat, const uint6
                               const uint64_t *s0e0, uint32_t max_mismatches, const uint64_t *out_off,
                               uint64_t total_intervals, uint64_t *out_s, uint64_t *out_e, uint64_t *out_edit);
 
+/* ---- the same search on 2-bit packed DNA patterns, one strand or both, in one pass ---- */
+/* What a read mapper asks for: the first max_hits intervals of every pattern (of each strand) and a flag when there
+ * were more.  Inputs are those of fmx_count_batch_packed2* -- the same word layout, absolute offsets, only words
+ * pat_off[0] / 32 .. (pat_off[npat] - 1) / 32 are read and their other bits influence nothing, an 8-byte aligned
+ * d_pat_words (FMX_ERR_ARG before any launch otherwise) -- without `s0e0`.
+ *
+ * The batch is nv virtual patterns: nv = npat and v = k for fmx_mismatch_hits_batch_packed2*; nv = 2 npat for the _rc
+ * calls, where virtual pattern 2k is P_k as written and 2k + 1 its reverse complement R, R[t] = 5 - P[m - 1 - t],
+ * exactly as in fmx_count_batch_packed2_rc.  For every virtual pattern the `enum` recursion above runs from (0, len) on
+ * its symbols (symbol = code + 1), in exactly that order:
+ *     out_nint[v], out_count[v]   what fmx_mismatch_count_batch gives on the bytes of the virtual pattern -- exact also
+ *                                 when more intervals exist than slots: the search keeps counting once its slots are full;
+ *     slot v * max_hits + j       of out_s / out_e: interval j, while j < max_hits; out_edit[2 slot + t] its edits in
+ *                                 fmx_mismatch_search_batch's format (pos << 32) | sym, pos counted from the start of the
+ *                                 VIRTUAL pattern (positions in R on an odd v), UINT64_MAX where unused;
+ *     slots min(nint, max_hits) .. max_hits - 1 of every virtual pattern are written too: s = e = 0 and both edit
+ *                                 words UINT64_MAX.
+ * out_nint / out_count have nv entries, out_s / out_e nv * max_hits, out_edit 2 * nv * max_hits; any of them may be
+ * NULL.  The whole out_s / out_e feed fmx_locate_batch* unchanged with npat = nv * max_hits.  max_hits = 0 is legal: only
+ * out_nint / out_count are written.  A code whose symbol is above max_character (alphabets of 2 or 3 symbols, single
+ * strand only) costs a substitution where it stands, as in the byte call; it is never FMX_ERR_SYMBOL_RANGE.
+ * Substitutions run over 1 .. max_character, also for max_character 5..7.
+ * Bad offsets are FMX_ERR_ARG: the pattern is never read, its nint and count are 0 and its slots hold the filler, on
+ * both strands.  max_mismatches > FMX_MAX_MISMATCHES, and a 2 * nv * max_hits that overflows 64 bits, are FMX_ERR_ARG
+ * before any launch.  Empty text: the offsets are still checked, everything is zero or filler.
+ * Served: the single-strand calls what fmx_packed2_supported() accepts, the _rc calls what fmx_packed2_rc_supported()
+ * accepts; indexes with the pair index or the k-mer table are served from their plain records.  Every other handle
+ * gets FMX_ERR_UNSUPPORTED and nothing is written.  The dev forms only launch kernels on `stream` -- no allocation, no
+ * synchronisation, capturable -- and report through fmx_stream_status(); the host forms upload the words and offsets
+ * once, launch once and bring the arrays down. */
+int fmx_mismatch_hits_batch_packed2_dev(const fmx_index *idx, const uint64_t *d_pat_words, const uint64_t *d_pat_off,
+                                        uint64_t npat, uint32_t max_mismatches, uint64_t max_hits, uint64_t *d_out_nint,
+                                        uint64_t *d_out_count, uint64_t *d_out_s, uint64_t *d_out_e,
+                                        uint64_t *d_out_edit, void *stream);
+int fmx_mismatch_hits_batch_packed2(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off,
+                                    uint64_t npat, uint32_t max_mismatches, uint64_t max_hits, uint64_t *out_nint,
+                                    uint64_t *out_count, uint64_t *out_s, uint64_t *out_e, uint64_t *out_edit);
+int fmx_mismatch_hits_batch_packed2_rc_dev(const fmx_index *idx, const uint64_t *d_pat_words, const uint64_t *d_pat_off,
+                                           uint64_t npat, uint32_t max_mismatches, uint64_t max_hits,
+                                           uint64_t *d_out_nint, uint64_t *d_out_count, uint64_t *d_out_s,
+                                           uint64_t *d_out_e, uint64_t *d_out_edit, void *stream);
+int fmx_mismatch_hits_batch_packed2_rc(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off,
+                                       uint64_t npat, uint32_t max_mismatches, uint64_t max_hits, uint64_t *out_nint,
+                                       uint64_t *out_count, uint64_t *out_s, uint64_t *out_e, uint64_t *out_edit);
+
 /* ---- backward matching statistics and super-maximal exact-match seeds ---- */
 /* An ADDITION with no counterpart in the crate: fmx_suffix_match_batch asked at EVERY end position of every pattern,
  * without copying the prefixes.  Pattern k = pat[pat_off[k] .. pat_off[k+1]) has m symbols; end position i (1 <= i <=
