@@ -274,6 +274,35 @@ class _Index:
         above max_character ends a pattern's match and is no error."""
         return _suffix_match(self, self._lib.fmx_suffix_match_batch, (self._h,), patterns, flat, off, s0e0, min_count)
 
+    def suffix_match_many_packed(self, words, off, s0e0=None, min_count=1):
+        """suffix_match_many on a 2-bit packed pattern stream (`pack2`; fmx_suffix_match_batch_packed2): the same
+        SearchBatch with `.lengths`.  `packed2_supported()` indexes only; any other raises ERR_UNSUPPORTED."""
+        return self._suffix_match_packed(words, off, s0e0, min_count, 1)
+
+    def suffix_match_many_packed_both_strands(self, words, off, min_count=1):
+        """both strands of every pattern of a 2-bit packed stream in one call (fmx_suffix_match_batch_packed2_rc): a
+        SearchBatch with `.lengths` of 2 * npat entries, entry 2k pattern k as written, entry 2k + 1 its reverse
+        complement (reversed, symbol c -> 5 - c), whose length is that of the matched PREFIX of the pattern.
+        `packed2_rc_supported()` indexes only; any other raises ERR_UNSUPPORTED."""
+        return self._suffix_match_packed(words, off, None, min_count, 2)
+
+    def _suffix_match_packed(self, words, off, s0e0, min_count, strands):
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        npat = len(off) - 1
+        if npat > 0 and int(off[-1]) > 32 * len(words):
+            raise Error(L.ERR_ARG, "off[-1] symbols do not fit %d words" % len(words))
+        nv = strands * npat
+        s, e, c, ln = (np.zeros(max(nv, 1), dtype=np.uint64) for _ in range(4))
+        if strands == 2:
+            _check(self._lib.fmx_suffix_match_batch_packed2_rc(self._h, _p(words), _p(off), npat, int(min_count),
+                                                               _p(s), _p(e), _p(c), _p(ln)))
+        else:
+            se = None if s0e0 is None else np.ascontiguousarray(s0e0, dtype=np.uint64)
+            _check(self._lib.fmx_suffix_match_batch_packed2(self._h, _p(words), _p(off), npat, _p(se), int(min_count),
+                                                            _p(s), _p(e), _p(c), _p(ln)))
+        return SearchBatch(self, s[:nv], e[:nv], c[:nv], ln[:nv])
+
     def mismatch_search_many(self, patterns=None, flat=None, off=None, s0e0=None, max_mismatches=1):
         """every interval of a variant of each pattern with at most `max_mismatches` (0, 1 or 2) substituted symbols,
         in the order of include/fmx.h (fmx_mismatch_count_batch, the scan, fmx_mismatch_search_batch): a MismatchBatch.

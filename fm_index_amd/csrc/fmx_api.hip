@@ -409,6 +409,30 @@ int fmx_suffix_match_batch_dev(const fmx_index *idx, const void *d_pat, const ui
   return fmx_launch_suffix_match(idx, d_pat, d_pat_off, npat, d_s0e0, min_count, d_out_s, d_out_e, d_out_count,
                                  d_out_len, (hipStream_t)stream);
 }
+// the packed forms: the handle is checked first (nothing is written for one the route does not serve), then the
+// arguments
+int fmx_suffix_match_batch_packed2_dev(const fmx_index *idx, const uint64_t *d_pat_words, const uint64_t *d_pat_off,
+                                       uint64_t npat, const uint64_t *d_s0e0, uint64_t min_count, uint64_t *d_out_s,
+                                       uint64_t *d_out_e, uint64_t *d_out_count, uint64_t *d_out_len, void *stream) {
+  CHECK_IDX(idx);
+  if (!fmx_packed2_served(idx))
+    return fail(FMX_ERR_UNSUPPORTED, "packed patterns need a one-level FM index over u8 symbols on the 32-bit engine");
+  if (npat && (!d_pat_off)) return fail(FMX_ERR_ARG, "pat_off is NULL");
+  if ((uintptr_t)d_pat_words & 7u) return fail(FMX_ERR_ARG, "pat_words is not 8-byte aligned");
+  return fmx_launch_sfx_packed2(idx, d_pat_words, d_pat_off, npat, d_s0e0, min_count, d_out_s, d_out_e, d_out_count,
+                                d_out_len, (hipStream_t)stream);
+}
+int fmx_suffix_match_batch_packed2_rc_dev(const fmx_index *idx, const uint64_t *d_pat_words, const uint64_t *d_pat_off,
+                                          uint64_t npat, uint64_t min_count, uint64_t *d_out_s, uint64_t *d_out_e,
+                                          uint64_t *d_out_count, uint64_t *d_out_len, void *stream) {
+  CHECK_IDX(idx);
+  if (!fmx_packed2_rc_served(idx))
+    return fail(FMX_ERR_UNSUPPORTED, "both-strand packed patterns need a packed-pattern index with max_character >= 4");
+  if (npat && (!d_pat_off)) return fail(FMX_ERR_ARG, "pat_off is NULL");
+  if ((uintptr_t)d_pat_words & 7u) return fail(FMX_ERR_ARG, "pat_words is not 8-byte aligned");
+  return fmx_launch_sfx_packed2_rc(idx, d_pat_words, d_pat_off, npat, min_count, d_out_s, d_out_e, d_out_count,
+                                   d_out_len, (hipStream_t)stream);
+}
 // what both passes and both forms of the mismatch search refuse before anything is launched
 #define CHECK_MISMATCH(idx, max_mismatches)                                                              \
   if ((max_mismatches) > FMX_MAX_MISMATCHES) return fail(FMX_ERR_ARG, "max_mismatches exceeds FMX_MAX_MISMATCHES"); \
@@ -1343,6 +1367,63 @@ int fmx_suffix_match_batch(const fmx_index *idx, const void *pat, const uint64_t
   if (out_count) FMX_HIP(hipMemcpyAsync(out_count, d_c, b_out, hipMemcpyDeviceToHost, S));
   if (out_len) FMX_HIP(hipMemcpyAsync(out_len, d_l, b_out, hipMemcpyDeviceToHost, S));
   return finish_host_call(sx);
+}
+// The longest-suffix match of a 2-bit packed pattern stream on host arrays: the staging of count_packed2_host's
+// retained-scratch path (the words that hold symbols pat_off[0] .. pat_off[npat] - 1 and the offsets go up once, the
+// kernels get the address the device copy would have if it began at word 0), one launch of fmx_packed_suffix.h's
+// kernels, four arrays of one entry per pattern -- two with `both` -- come down.  No chunk pipeline, no arena path.
+static int sfx_packed2_host(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off, uint64_t npat,
+                            const uint64_t *s0e0, uint64_t min_count, uint64_t *out_s, uint64_t *out_e,
+                            uint64_t *out_count, uint64_t *out_len, bool both) {
+  CHECK_IDX(idx);
+  if (both ? !fmx_packed2_rc_served(idx) : !fmx_packed2_served(idx))
+    return fail(FMX_ERR_UNSUPPORTED, both ? "both-strand packed patterns need a packed-pattern index with max_character >= 4"
+                                          : "packed patterns need a one-level FM index over u8 symbols on the 32-bit engine");
+  if (npat == 0) return FMX_OK;
+  if (!pat_off) return fail(FMX_ERR_ARG, "pat_off is NULL");
+  const uint64_t total = pat_off[npat], first = pat_off[0];
+  if (first > total) return fail(FMX_ERR_ARG, "pat_off is not non-decreasing");
+  if (total > first && !pat_words) return fail(FMX_ERR_ARG, "pat_words is NULL");
+  const uint64_t w0 = first >> 5, nwords = total > first ? ((total - 1) >> 5) - w0 + 1 : 0;
+  const size_t b_words = (size_t)nwords * 8, b_out = (size_t)npat * (both ? 16 : 8), b_off = (size_t)(npat + 1) * 8,
+               b_se = s0e0 ? (size_t)npat * 16 : 0;
+  HostCall hc;
+  FMX_HIP(hc.open(idx->device, HostCall::pad(b_words) + HostCall::pad(b_off) + (s0e0 ? HostCall::pad(b_se) : 0) +
+                                   4 * HostCall::pad(b_out)));
+  uint64_t *d_words = hc.take<uint64_t>(b_words), *d_off = hc.take<uint64_t>(b_off);
+  uint64_t *d_se = s0e0 ? hc.take<uint64_t>(b_se) : nullptr;
+  uint64_t *d_s = hc.take<uint64_t>(b_out), *d_e = hc.take<uint64_t>(b_out), *d_c = hc.take<uint64_t>(b_out);
+  uint64_t *d_l = hc.take<uint64_t>(b_out);
+  SmallCtx *sx = hc.sx;
+  hipStream_t S = sx->st;
+  CallStatus cs(sx);
+  FMX_HIP(hipMemsetAsync(status_dev(sx), 0, 4, S));
+  if (b_words) FMX_HIP(hipMemcpyAsync(d_words, pat_words + w0, b_words, hipMemcpyHostToDevice, S));
+  FMX_HIP(hipMemcpyAsync(d_off, pat_off, b_off, hipMemcpyHostToDevice, S));
+  if (s0e0) FMX_HIP(hipMemcpyAsync(d_se, s0e0, b_se, hipMemcpyHostToDevice, S));
+  // (virtual: word 0 of the caller's buffer -- never dereferenced below word `w0`)
+  uint64_t *r_s = out_s ? d_s : nullptr, *r_e = out_e ? d_e : nullptr, *r_c = out_count ? d_c : nullptr,
+           *r_l = out_len ? d_l : nullptr;
+  if (int rc = both ? fmx_launch_sfx_packed2_rc(idx, d_words - w0, d_off, npat, min_count, r_s, r_e, r_c, r_l, S)
+                    : fmx_launch_sfx_packed2(idx, d_words - w0, d_off, npat, d_se, min_count, r_s, r_e, r_c, r_l, S)) {
+    (void)hipStreamSynchronize(S);
+    return rc;
+  }
+  if (out_s) FMX_HIP(hipMemcpyAsync(out_s, d_s, b_out, hipMemcpyDeviceToHost, S));
+  if (out_e) FMX_HIP(hipMemcpyAsync(out_e, d_e, b_out, hipMemcpyDeviceToHost, S));
+  if (out_count) FMX_HIP(hipMemcpyAsync(out_count, d_c, b_out, hipMemcpyDeviceToHost, S));
+  if (out_len) FMX_HIP(hipMemcpyAsync(out_len, d_l, b_out, hipMemcpyDeviceToHost, S));
+  return finish_host_call(sx);
+}
+int fmx_suffix_match_batch_packed2(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off,
+                                   uint64_t npat, const uint64_t *s0e0, uint64_t min_count, uint64_t *out_s,
+                                   uint64_t *out_e, uint64_t *out_count, uint64_t *out_len) {
+  return sfx_packed2_host(idx, pat_words, pat_off, npat, s0e0, min_count, out_s, out_e, out_count, out_len, false);
+}
+int fmx_suffix_match_batch_packed2_rc(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off,
+                                      uint64_t npat, uint64_t min_count, uint64_t *out_s, uint64_t *out_e,
+                                      uint64_t *out_count, uint64_t *out_len) {
+  return sfx_packed2_host(idx, pat_words, pat_off, npat, nullptr, min_count, out_s, out_e, out_count, out_len, true);
 }
 // The two passes of the mismatch search on host arrays: upload, one launch, download, like fmx_suffix_match_batch.
 // write = false: out_a / out_b = out_nint / out_count (npat entries).  write = true: out_a / out_b / out_edit = out_s /

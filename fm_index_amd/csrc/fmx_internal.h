@@ -400,6 +400,15 @@ bool fmx_packed2_rc_served(const fmx_index *idx);
 int fmx_launch_suffix_match(const fmx_index *idx, const void *d_pat, const uint64_t *d_off, uint64_t npat,
                             const uint64_t *d_s0e0, uint64_t min_count, uint64_t *d_s, uint64_t *d_e,
                             uint64_t *d_cnt, uint64_t *d_len, hipStream_t st);
+// fmx_launch_suffix_match on a 2-bit packed pattern stream (fmx_packed_suffix.h): fmx_packed2_served() handles, and
+// FMX_ERR_UNSUPPORTED, nothing launched, for any other.  _rc: both strands in one launch, outputs of 2 npat entries
+// (slot 2k the pattern, slot 2k + 1 its reverse complement), no start pairs; fmx_packed2_rc_served() handles.
+int fmx_launch_sfx_packed2(const fmx_index *idx, const uint64_t *d_words, const uint64_t *d_off, uint64_t npat,
+                           const uint64_t *d_s0e0, uint64_t min_count, uint64_t *d_s, uint64_t *d_e, uint64_t *d_cnt,
+                           uint64_t *d_len, hipStream_t st);
+int fmx_launch_sfx_packed2_rc(const fmx_index *idx, const uint64_t *d_words, const uint64_t *d_off, uint64_t npat,
+                              uint64_t min_count, uint64_t *d_s, uint64_t *d_e, uint64_t *d_cnt, uint64_t *d_len,
+                              hipStream_t st);
 // backward search with up to max_mismatches (<= FMX_MAX_MISMATCHES) substitutions, 32-bit engine only (fmx_mismatch.h).
 // write = false: pass 1, d_nint[k] / d_cnt[k] = intervals emitted / their rows; write = true: pass 2, interval j of
 // pattern k to slot d_out_off[k] + j of d_s / d_e / d_edit (2 entries per slot), never outside the pattern's own

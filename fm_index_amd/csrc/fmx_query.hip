@@ -2882,6 +2882,7 @@ int fmx_launch_count(const fmx_index *idx, const void *d_pat, const uint64_t *d_
 #include "fmx_suffix.h"     // fmx_launch_suffix_match: the longest-suffix-match twins of the count kernels
 #include "fmx_packed.h"     // fmx_launch_count_packed2: the count twins that read 2-bit packed DNA patterns
 #include "fmx_packed_rc.h"  // fmx_launch_count_packed2_rc: both strands of every packed pattern in one launch
+#include "fmx_packed_suffix.h"   // fmx_launch_sfx_packed2[_rc]: the longest-suffix match on packed patterns
 #include "fmx_mismatch.h"   // fmx_launch_mismatch: backward search with up to FMX_MAX_MISMATCHES substitutions
 #include "fmx_mstats.h"     // fmx_launch_match_stats: matching statistics of every pattern prefix, and the seed filter
 #include "fmx_packed_mstats.h"   // fmx_launch_match_stats_packed2: the same on packed patterns, one strand or both

@@ -332,6 +332,41 @@ int fmx_suffix_match_batch(const fmx_index *idx, const void *pat, const uint64_t
                            const uint64_t *s0e0, uint64_t min_count, uint64_t *out_s, uint64_t *out_e,
                            uint64_t *out_count, uint64_t *out_len);
 
+/* ---- the same on 2-bit packed DNA patterns, one strand or both ---------------- */
+/* fmx_suffix_match_batch* for the pattern form of fmx_count_batch_packed2*: the same word layout and absolute
+ * offsets, only words pat_off[0] / 32 .. (pat_off[npat] - 1) / 32 are read and their other bits influence nothing,
+ * d_pat_words 8-byte aligned (FMX_ERR_ARG before any launch otherwise).
+ *
+ * fmx_suffix_match_batch_packed2*: outputs and status are bit-identical to fmx_suffix_match_batch* on the unpacked
+ * bytes (symbol = code + 1): the loop above with min_count 0 treated as 1; L = 0 and the start pair for an empty
+ * pattern, for a start pair below min_count or with e < s, and on an empty text (where everything is 0 and the
+ * offsets are still checked); FMX_ERR_ARG for bad offsets and for an `s0e0` entry above len() (such a pattern is never
+ * read, its four outputs are 0).  A code whose symbol is above max_character (alphabets of 2 or 3 symbols) ends that
+ * pattern's match and is NOT FMX_ERR_SYMBOL_RANGE.  Any output array may be NULL.  Served: what
+ * fmx_packed2_supported() accepts.
+ *
+ * fmx_suffix_match_batch_packed2_rc*: both strands from the same words, no `s0e0`.  The arrays hold 2 npat entries:
+ * slot 2k is pattern k as written, slot 2k + 1 its reverse complement R, R[t] = 5 - P[m - 1 - t], exactly as in
+ * fmx_count_batch_packed2_rc.  out_len of an odd slot counts symbols of R: the length of the matched PREFIX of P,
+ * complemented.  Bad offsets zero both slots.  R is formed in registers; the words and offsets cross the host link
+ * once.  Served: what fmx_packed2_rc_supported() accepts.
+ *
+ * Every other handle gets FMX_ERR_UNSUPPORTED and nothing is written.  The dev forms only launch kernels on `stream`
+ * (no allocation, no synchronisation, capturable) and report through fmx_stream_status(); the host forms upload the
+ * words and offsets once, launch once and bring the arrays down. */
+int fmx_suffix_match_batch_packed2_dev(const fmx_index *idx, const uint64_t *d_pat_words, const uint64_t *d_pat_off,
+                                       uint64_t npat, const uint64_t *d_s0e0, uint64_t min_count, uint64_t *d_out_s,
+                                       uint64_t *d_out_e, uint64_t *d_out_count, uint64_t *d_out_len, void *stream);
+int fmx_suffix_match_batch_packed2(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off,
+                                   uint64_t npat, const uint64_t *s0e0, uint64_t min_count, uint64_t *out_s,
+                                   uint64_t *out_e, uint64_t *out_count, uint64_t *out_len);
+int fmx_suffix_match_batch_packed2_rc_dev(const fmx_index *idx, const uint64_t *d_pat_words, const uint64_t *d_pat_off,
+                                          uint64_t npat, uint64_t min_count, uint64_t *d_out_s, uint64_t *d_out_e,
+                                          uint64_t *d_out_count, uint64_t *d_out_len, void *stream);
+int fmx_suffix_match_batch_packed2_rc(const fmx_index *idx, const uint64_t *pat_words, const uint64_t *pat_off,
+                                      uint64_t npat, uint64_t min_count, uint64_t *out_s, uint64_t *out_e,
+                                      uint64_t *out_count, uint64_t *out_len);
+
 /* ---- backward search with up to two substituted symbols ---- */
 /* An ADDITION with no counterpart in the crate; the closest is Search::search (wrapper.rs:99-124) on every variant of
  * the pattern that differs from it in at most `max_mismatches` symbols.  For pattern P = pat[pat_off[k] ..
