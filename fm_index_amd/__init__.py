@@ -268,6 +268,35 @@ class _Index:
         """does this index take `search_many_packed_both_strands` (packed patterns, max_character >= 4)?"""
         return bool(self._lib.fmx_packed2_rc_supported(self._h))
 
+    def count_windows_packed(self, words, off, k):
+        """every length-k window of the sequences of a 2-bit packed stream (`pack2`; fmx_count_windows_packed2): a
+        SearchBatch with one slot per sequence symbol, slot off[i] - off[0] + j the window [j, j + k) of sequence i, and
+        `.valid` (bool) marking the slots that have a window -- the others hold (0, 0, 0).  `packed2_supported()`
+        indexes only; any other raises ERR_UNSUPPORTED."""
+        return self._count_windows_packed(words, off, k, 1)
+
+    def count_windows_packed_both_strands(self, words, off, k):
+        """the same on both strands in one call (fmx_count_windows_packed2_rc): two slots per sequence symbol, slot 2t
+        the window as written, slot 2t + 1 its reverse complement (reversed, symbol c -> 5 - c); a canonical k-mer
+        count is the sum of the two.  `packed2_rc_supported()` indexes only; any other raises ERR_UNSUPPORTED."""
+        return self._count_windows_packed(words, off, k, 2)
+
+    def _count_windows_packed(self, words, off, k, strands):
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        nseq = len(off) - 1
+        if nseq > 0 and int(off[-1]) > 32 * len(words):
+            raise Error(L.ERR_ARG, "off[-1] symbols do not fit %d words" % len(words))
+        total = int(off[-1] - off[0]) if nseq > 0 and off[-1] >= off[0] else 0
+        s, e, c = (np.zeros(max(strands * total, 1), dtype=np.uint64) for _ in range(3))
+        call = self._lib.fmx_count_windows_packed2_rc if strands == 2 else self._lib.fmx_count_windows_packed2
+        _check(call(self._h, _p(words), _p(off), nseq, int(k), _p(s), _p(e), _p(c)))
+        t = np.arange(total, dtype=np.int64)                        # (the call has checked the offsets)
+        o = off.astype(np.int64) - int(off[0])
+        valid = t + int(k) <= o[np.searchsorted(o, t, side="right")] if total else np.zeros(0, dtype=bool)
+        return SearchBatch(self, s[:strands * total], e[:strands * total], c[:strands * total],
+                           valid=np.repeat(valid, strands))
+
     def suffix_match_many(self, patterns=None, flat=None, off=None, s0e0=None, min_count=1):
         """longest suffix of every pattern whose interval keeps >= min_count rows (fmx_suffix_match_batch): a
         SearchBatch of that interval with `.lengths` (numpy u64), so `.locate()` gives the seed positions.  A symbol
@@ -846,14 +875,16 @@ class MatchStatsBatch:
 
 class SearchBatch:
     """Result of search_many: per-pattern (s, e, count) arrays (numpy u64); of suffix_match_many: the same for the
-    longest matching suffix, plus `lengths` (symbols matched; None after search_many)."""
+    longest matching suffix, plus `lengths` (symbols matched; None after search_many); of count_windows_packed*: one
+    entry per slot, plus `valid` (bool: the slot has a window; None otherwise)."""
 
-    def __init__(self, index, s, e, counts, lengths=None):
+    def __init__(self, index, s, e, counts, lengths=None, valid=None):
         self._ix = index
         self.s = s
         self.e = e
         self.counts = counts
         self.lengths = lengths
+        self.valid = valid
 
     def count(self):
         return self.counts

@@ -79,6 +79,10 @@ SYMBOLS = [
     ("fmx_count_batch_packed2_rc_dev", _I, [_V, _V, _V, _U64, _V, _V, _V, _V]),
     ("fmx_count_batch_packed2_rc", _I, [_V, _V, _V, _U64, _V, _V, _V]),
     ("fmx_packed2_rc_supported", _I, [_V]),
+    ("fmx_count_windows_packed2_dev", _I, [_V, _V, _V, _U64, _U64, _U64, _V, _V, _V, _V]),
+    ("fmx_count_windows_packed2", _I, [_V, _V, _V, _U64, _U64, _V, _V, _V]),
+    ("fmx_count_windows_packed2_rc_dev", _I, [_V, _V, _V, _U64, _U64, _U64, _V, _V, _V, _V]),
+    ("fmx_count_windows_packed2_rc", _I, [_V, _V, _V, _U64, _U64, _V, _V, _V]),
     ("fmx_suffix_match_batch_dev", _I, [_V, _V, _V, _U64, _V, _U64, _V, _V, _V, _V, _V]),
     ("fmx_suffix_match_batch", _I, [_V, _V, _V, _U64, _V, _U64, _V, _V, _V, _V]),
     ("fmx_suffix_match_batch_packed2_dev", _I, [_V, _V, _V, _U64, _V, _U64, _V, _V, _V, _V, _V]),

@@ -555,6 +555,38 @@ int fmx_match_stats_batch_packed2_rc_dev(const fmx_index *idx, const uint64_t *d
   return match_stats_packed2_dev(idx, d_pat_words, d_pat_off, npat, total_syms, min_count, max_len, min_seed_len,
                                  d_out_s, d_out_e, d_out_len, true, stream);
 }
+// every length-k window of packed sequences: what both forms refuse before anything is launched -- the handle first
+// (nothing is written for one the route does not serve), then the arguments
+#define CHECK_WINDOWS_P2(idx, k, out_count, both)                                                                  \
+  if ((both) ? !fmx_packed2_rc_served(idx) : !fmx_packed2_served(idx))                                              \
+    return fail(FMX_ERR_UNSUPPORTED, (both) ? "both-strand packed patterns need a packed-pattern index with max_character >= 4" \
+                                            : "packed patterns need a one-level FM index over u8 symbols on the 32-bit engine"); \
+  if ((k) == 0 || (k) > 0xFFFFFFFFull) return fail(FMX_ERR_ARG, "k is not in [1, 2^32)");                           \
+  if (!(out_count)) return fail(FMX_ERR_ARG, "out_count is NULL")
+static int count_windows_packed2_dev(const fmx_index *idx, const uint64_t *d_seq_words, const uint64_t *d_seq_off,
+                                     uint64_t nseq, uint64_t total_syms, uint64_t k, uint64_t *d_out_s,
+                                     uint64_t *d_out_e, uint64_t *d_out_count, bool both, void *stream) {
+  CHECK_IDX(idx);
+  CHECK_WINDOWS_P2(idx, k, d_out_count, both);
+  if ((uintptr_t)d_seq_words & 7u) return fail(FMX_ERR_ARG, "seq_words is not 8-byte aligned");
+  if (nseq == 0)                                     // no sequence, no slot
+    return total_syms ? fail(FMX_ERR_ARG, "total_syms is not seq_off[nseq] - seq_off[0]") : FMX_OK;
+  if (!d_seq_off) return fail(FMX_ERR_ARG, "seq_off is NULL");
+  return fmx_launch_count_windows_packed2(idx, d_seq_words, d_seq_off, nseq, total_syms, k, d_out_s, d_out_e,
+                                          d_out_count, both, (hipStream_t)stream);
+}
+int fmx_count_windows_packed2_dev(const fmx_index *idx, const uint64_t *d_seq_words, const uint64_t *d_seq_off,
+                                  uint64_t nseq, uint64_t total_syms, uint64_t k, uint64_t *d_out_s, uint64_t *d_out_e,
+                                  uint64_t *d_out_count, void *stream) {
+  return count_windows_packed2_dev(idx, d_seq_words, d_seq_off, nseq, total_syms, k, d_out_s, d_out_e, d_out_count,
+                                   false, stream);
+}
+int fmx_count_windows_packed2_rc_dev(const fmx_index *idx, const uint64_t *d_seq_words, const uint64_t *d_seq_off,
+                                     uint64_t nseq, uint64_t total_syms, uint64_t k, uint64_t *d_out_s,
+                                     uint64_t *d_out_e, uint64_t *d_out_count, void *stream) {
+  return count_windows_packed2_dev(idx, d_seq_words, d_seq_off, nseq, total_syms, k, d_out_s, d_out_e, d_out_count,
+                                   true, stream);
+}
 int fmx_offsets_dev(const fmx_index *idx, const uint64_t *d_s, const uint64_t *d_e, uint64_t npat,
                     uint64_t *d_out_off, void *stream) {
   CHECK_IDX(idx);
@@ -1595,6 +1627,52 @@ int fmx_match_stats_batch_packed2_rc(const fmx_index *idx, const uint64_t *pat_w
                                      uint64_t *out_s, uint64_t *out_e, uint64_t *out_len) {
   return match_stats_packed2_host(idx, pat_words, pat_off, npat, min_count, max_len, min_seed_len, out_s, out_e,
                                   out_len, true);
+}
+// The count of every length-k window of 2-bit packed sequences on host arrays: the staging of match_stats_packed2_host
+// (the words that hold symbols seq_off[0] .. seq_off[nseq] - 1 and the offsets go up once, the kernels get the address
+// the device copy would have if it began at word 0), the kernels of fmx_packed_windows.h, three arrays of one entry per
+// sequence symbol -- per strand with `both` -- come down.  No chunk pipeline.
+static int count_windows_packed2_host(const fmx_index *idx, const uint64_t *seq_words, const uint64_t *seq_off,
+                                      uint64_t nseq, uint64_t k, uint64_t *out_s, uint64_t *out_e, uint64_t *out_count,
+                                      bool both) {
+  CHECK_IDX(idx);
+  CHECK_WINDOWS_P2(idx, k, out_count, both);
+  if (nseq == 0) return FMX_OK;
+  if (!seq_off) return fail(FMX_ERR_ARG, "seq_off is NULL");
+  const uint64_t total = seq_off[nseq], first = seq_off[0];
+  if (first > total) return fail(FMX_ERR_ARG, "seq_off is not non-decreasing");
+  const uint64_t span = total - first;
+  if (span && !seq_words) return fail(FMX_ERR_ARG, "seq_words is NULL");
+  const uint64_t w0 = first >> 5, nwords = span ? ((total - 1) >> 5) - w0 + 1 : 0;
+  const size_t b_words = (size_t)nwords * 8, b_out = (size_t)span * (both ? 16 : 8), b_off = (size_t)(nseq + 1) * 8;
+  HostCall hc;
+  FMX_HIP(hc.open(idx->device, HostCall::pad(b_words) + HostCall::pad(b_off) + 3 * (HostCall::pad(b_out) + 256)));
+  uint64_t *d_words = hc.take<uint64_t>(b_words), *d_off = hc.take<uint64_t>(b_off);
+  uint64_t *d_s = hc.take<uint64_t>(b_out), *d_e = hc.take<uint64_t>(b_out), *d_c = hc.take<uint64_t>(b_out);
+  SmallCtx *sx = hc.sx;
+  hipStream_t S = sx->st;
+  CallStatus cs(sx);
+  FMX_HIP(hipMemsetAsync(status_dev(sx), 0, 4, S));
+  if (b_words) FMX_HIP(hipMemcpyAsync(d_words, seq_words + w0, b_words, hipMemcpyHostToDevice, S));
+  FMX_HIP(hipMemcpyAsync(d_off, seq_off, b_off, hipMemcpyHostToDevice, S));
+  // (virtual: word 0 of the caller's buffer -- never dereferenced below word `w0`)
+  if (int rc = fmx_launch_count_windows_packed2(idx, d_words - w0, d_off, nseq, span, k, out_s ? d_s : nullptr,
+                                                out_e ? d_e : nullptr, d_c, both, S)) {
+    (void)hipStreamSynchronize(S);
+    return rc;
+  }
+  if (out_s && b_out) FMX_HIP(hipMemcpyAsync(out_s, d_s, b_out, hipMemcpyDeviceToHost, S));
+  if (out_e && b_out) FMX_HIP(hipMemcpyAsync(out_e, d_e, b_out, hipMemcpyDeviceToHost, S));
+  if (b_out) FMX_HIP(hipMemcpyAsync(out_count, d_c, b_out, hipMemcpyDeviceToHost, S));
+  return finish_host_call(sx);
+}
+int fmx_count_windows_packed2(const fmx_index *idx, const uint64_t *seq_words, const uint64_t *seq_off, uint64_t nseq,
+                              uint64_t k, uint64_t *out_s, uint64_t *out_e, uint64_t *out_count) {
+  return count_windows_packed2_host(idx, seq_words, seq_off, nseq, k, out_s, out_e, out_count, false);
+}
+int fmx_count_windows_packed2_rc(const fmx_index *idx, const uint64_t *seq_words, const uint64_t *seq_off, uint64_t nseq,
+                                 uint64_t k, uint64_t *out_s, uint64_t *out_e, uint64_t *out_count) {
+  return count_windows_packed2_host(idx, seq_words, seq_off, nseq, k, out_s, out_e, out_count, true);
 }
 // The packed one-pass mismatch search on host arrays: the staging of match_stats_packed2_host (the words that hold
 // symbols pat_off[0] .. pat_off[npat] - 1 and the offsets go up once, the kernel gets the address the device copy would

@@ -430,6 +430,13 @@ int fmx_launch_match_stats(const fmx_index *idx, const void *d_pat, const uint64
 int fmx_launch_match_stats_packed2(const fmx_index *idx, const uint64_t *d_words, const uint64_t *d_off, uint64_t npat,
                                    uint64_t total, uint64_t min_count, uint64_t max_len, uint64_t min_seed_len,
                                    uint64_t *d_s, uint64_t *d_e, uint64_t *d_len, bool both, hipStream_t st);
+// the count of every length-k window of 2-bit packed sequences (fmx_packed_windows.h): slot t is the window that starts
+// at symbol d_off[0] + t; both = true: slots 2t / 2t + 1 the window and its reverse complement, arrays of 2 total
+// entries.  The caller has checked the handle (fmx_packed2_served / fmx_packed2_rc_served), d_cnt != NULL and
+// 1 <= k < 2^32.  `total` is the span of the offsets either way.  nseq > 0.
+int fmx_launch_count_windows_packed2(const fmx_index *idx, const uint64_t *d_words, const uint64_t *d_off,
+                                     uint64_t nseq, uint64_t total, uint64_t k, uint64_t *d_s, uint64_t *d_e,
+                                     uint64_t *d_cnt, bool both, hipStream_t st);
 // the mismatch search on a 2-bit packed pattern stream in one pass (fmx_packed_mismatch.h): virtual pattern v (k, or
 // 2 k + strand with both = true) gets d_nint[v] / d_cnt[v] and its first max_hits intervals in slots v * max_hits ..
 // of d_s / d_e / d_edit (2 entries per slot), the unused ones filled.  The caller has checked the handle

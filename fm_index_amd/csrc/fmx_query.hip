@@ -2886,6 +2886,7 @@ int fmx_launch_count(const fmx_index *idx, const void *d_pat, const uint64_t *d_
 #include "fmx_mismatch.h"   // fmx_launch_mismatch: backward search with up to FMX_MAX_MISMATCHES substitutions
 #include "fmx_mstats.h"     // fmx_launch_match_stats: matching statistics of every pattern prefix, and the seed filter
 #include "fmx_packed_mstats.h"   // fmx_launch_match_stats_packed2: the same on packed patterns, one strand or both
+#include "fmx_packed_windows.h"  // fmx_launch_count_windows_packed2: every length-k window of packed sequences
 #include "fmx_packed_mismatch.h" // fmx_launch_mismatch_hits_packed2: one-pass mismatch search on packed patterns
 
 uint64_t fmx_offsets_tile_bytes(uint64_t npat) {

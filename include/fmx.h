@@ -306,6 +306,41 @@ int fmx_count_batch_packed2_rc(const fmx_index *idx, const uint64_t *pat_words, 
                                uint64_t *out_s, uint64_t *out_e, uint64_t *out_count);
 int fmx_packed2_rc_supported(const fmx_index *idx);   /* 1: this index takes the two calls above */
 
+/* ---- every length-k window of packed sequences, one strand or both ----------- */
+/* A k-mer scan: how often does every window of k symbols of a sequence occur in the text?  Patterns of the calls above
+ * cannot overlap, so a scan through them writes every window out (16 bytes per window at k = 32); here the sequence
+ * itself is the input, 0.25 bytes per window.
+ * Input: the packed layout of fmx_count_batch_packed2*, unchanged.  Sequence i is symbols [seq_off[i], seq_off[i+1])
+ * in absolute numbering (a slice keeps its offsets); only words seq_off[0] / 32 .. (seq_off[nseq] - 1) / 32 are read
+ * and their other bits influence nothing; d_seq_words must be 8-byte aligned; total_syms is seq_off[nseq] - seq_off[0].
+ * Slots are numbered by the window's START: slot t = seq_off[i] - seq_off[0] + j is the window [j, j + k) of sequence
+ * i.  The arrays have total_syms entries.  The last k - 1 slots of every sequence have no window and hold (0, 0, 0) --
+ * for a sequence shorter than k that is all of its slots.  Nothing outside [0, total_syms) is written.
+ * Every slot that has a window holds exactly what fmx_count_batch_packed2 returns for that window given as a pattern
+ * of its own from (0, len): the (s, e) pair left by the early exit, and FMX_ERR_SYMBOL_RANGE on alphabets of 2 or 3
+ * symbols when a code with code + 1 > max_character is reached (that window's outputs are 0).
+ * fmx_count_windows_packed2_rc*: the arrays have 2 * total_syms entries; slot 2t is the window as written, slot 2t + 1
+ * its reverse complement R, R[x] = 5 - W[k - 1 - x]: what fmx_count_batch gives on the bytes of R from (0, len), as
+ * slot 2k + 1 of fmx_count_batch_packed2_rc does.  A canonical k-mer count is the sum of the two slots.
+ * FMX_ERR_ARG before any launch (nothing is written): k == 0, k >= 2^32, out_count == NULL (it carries the call's
+ * state; out_s and out_e may be NULL), a misaligned d_seq_words, and nseq == 0 with total_syms != 0.  Bad offsets, or
+ * a total_syms that is not the span of the offsets, are FMX_ERR_ARG through the status word: the slots of such a
+ * sequence hold 0 and it is never read.  An empty text, nseq == 0 and total_syms == 0 are fine.
+ * Served: the plain calls what fmx_packed2_supported() accepts, the _rc calls what fmx_packed2_rc_supported()
+ * accepts; every other handle gets FMX_ERR_UNSUPPORTED and nothing is written.
+ * The dev forms allocate nothing and never synchronise (kernels on `stream` only), can be captured and report through
+ * fmx_stream_status(); the host forms upload the words and offsets once, run the same kernels and synchronise. */
+int fmx_count_windows_packed2_dev(const fmx_index *idx, const uint64_t *d_seq_words, const uint64_t *d_seq_off,
+                                  uint64_t nseq, uint64_t total_syms, uint64_t k, uint64_t *d_out_s, uint64_t *d_out_e,
+                                  uint64_t *d_out_count, void *stream);
+int fmx_count_windows_packed2(const fmx_index *idx, const uint64_t *seq_words, const uint64_t *seq_off, uint64_t nseq,
+                              uint64_t k, uint64_t *out_s, uint64_t *out_e, uint64_t *out_count);
+int fmx_count_windows_packed2_rc_dev(const fmx_index *idx, const uint64_t *d_seq_words, const uint64_t *d_seq_off,
+                                     uint64_t nseq, uint64_t total_syms, uint64_t k, uint64_t *d_out_s,
+                                     uint64_t *d_out_e, uint64_t *d_out_count, void *stream);
+int fmx_count_windows_packed2_rc(const fmx_index *idx, const uint64_t *seq_words, const uint64_t *seq_off, uint64_t nseq,
+                                 uint64_t k, uint64_t *out_s, uint64_t *out_e, uint64_t *out_count);
+
 /* ---- longest suffix of a pattern that occurs: its interval and its length ---- */
 /* An ADDITION with no counterpart in the crate; the closest is Search::search (wrapper.rs:99-124) repeated one
  * symbol at a time until count() falls below min_count.  For pattern k = pat[pat_off[k] .. pat_off[k+1]) and
